@@ -7,12 +7,17 @@ for waves of long frames, the non-temporal write pass) — over one batch of syn
 already resident in HBM.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1] [--packets n] [--no-cpu]
-                  [--op update|l3fwd|flowkey|vlan] [--strong]
+                  [--op update|l3fwd|flowkey|vlan] [--strong] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line with the headline figure
+(`value`, `ms_per_step`); `--dump-outputs DIR` also writes what the last timed step computed
+(dump_outputs). Everything else described below — reference digests (`parity`), `roofline`,
+`stream_ceiling`, the sub-lines, `cpu_baseline` — is measured after that, only with `--full`.
 
 Workloads (BASELINE.json configs):
   N = 1   config C1: 1M x 1500 B IPv4+UDP (configs[1]). The timed calls rotate over 4 separately
           generated batches (2 above 1M packets), so no call re-processes what the previous one just
-          wrote (a NIC ring's steady state; --batches 1 replays one batch). The line also carries the
+          wrote (a NIC ring's steady state; --batches 1 replays one batch). With --full the line carries the
           one-batch `replay` sub-line, the `c4_shard` sub-line (the per-GPU batch of N > 1), the
           `c3` and `l3fwd_c3` sub-lines (config C3's 4M-frame mix through the update and the fused
           forward) and the `host` sub-line (the same frames in host memory through nfcs_update_host,
@@ -55,6 +60,8 @@ STREAM_READ_GBPS = 7007.0
 DEFAULT_PACKETS = {0: 1024, 1: 1 << 20, 2: 1 << 20, 3: 1 << 22}
 C4_PACKETS_PER_GPU = 1 << 22
 FRESH_BATCHES = 4
+# tests/cpp/netflow_adapter_test.cpp over the reference's own headers (built by oracle/Makefile)
+ADAPTER_EXE = os.path.join(ROOT, "oracle", "_ref", "netflow_adapter_test")
 NAMES = {0: "C0: {n} x 64 B IPv4 (header checksum only)",
          1: "C1: {n} x 1500 B IPv4+UDP, device-resident",
          2: "C2: {n} x 9000 B IPv4+TCP jumbo, device-resident",
@@ -428,6 +435,14 @@ def make_parser() -> argparse.ArgumentParser:
                          "launch shape follows the batch's mean footprint")
     ap.add_argument("--warm-seconds", type=float, default=0.5,
                     help="minimum untimed warm-up time (on top of --warmup steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else the line can carry: "
+                         "reference digests, the roofline (HIP events), the read-only stream ceiling, the replay / "
+                         "C4-shard / C3 / host-memory sub-lines, the other scope lines and the CPU baseline "
+                         "(each still switched off by its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                         "(float32; a fixed, seeded sample of the batch; see dump_outputs)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--batches", type=int, default=0,
                     help="update: batches the timed calls rotate over (default 4 up to 1M packets, 2 "
@@ -481,8 +496,8 @@ def main():
     # (run after the device-resident lines, the same binary measured 29 against 47 GB/s standalone:
     # profiles/r05_b_*)
     host_adapter = host_bursts = None
-    if (ws == 1 and args.op == "update" and args.config == 1 and not args.packets and not args.no_c4
-            and not args.no_host):
+    if (args.full and ws == 1 and args.op == "update" and args.config == 1 and not args.packets
+            and not args.no_c4 and not args.no_host):
         host_adapter = host_adapter_line(DEFAULT_PACKETS[1])
         host_bursts = host_bursts_line(DEFAULT_PACKETS[1])
     # NFCS_BENCH_DEVICE pins every rank to one device: rehearsing the N-rank path on a 1-GPU box
@@ -599,6 +614,47 @@ def main():
     ms_per_step = wall / args.steps * 1e3
     total_frame_bytes = D.sum(frame_bytes)
     rank_gbps = D.gather(frame_bytes / ((t1 - t0) / args.steps) / 1e9)
+    total_packets = D.sum(float(n))
+    out = {
+        "metric": ("flow keys + hash_flow per second, batched packets, MI355X" if fk else
+                   "device-resident payload GB/s checksummed, batched packets, 1/2/4/8 MI355X"
+                   + (" (fused L3 forward: TTL--, MAC rewrite, checksums)" if l3 else "")
+                   + (" (VLAN push/pop + checksums)" if args.op == "vlan" else "")),
+        "value": round(total_packets / (wall / args.steps) / 1e6, 2) if fk else
+                 round(total_frame_bytes / (wall / args.steps) / 1e9, 2),
+        "unit": "Mpkt/s" if fk else "GB/s",
+        "n_gpus": ws,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "u16 one's-complement (u8 frames, u32 word sums)",
+        "data": "synthetic (seeded generator, DESIGN.md §6), generated in HBM",
+        "config": {"workload": workload
+                   + (", fused L3 forward (next hop i % 9)" if l3 else "")
+                   + (", flow keys (header line only)" if fk else "")
+                   + (", push_vlan(100, 3) / pop_vlan() alternating, 1536-byte buffers"
+                      if args.op == "vlan" else ""),
+                   "packets_per_gpu": n, "frame_align": args.align,
+                   "frame_bytes_per_gpu": int(frame_bytes), "parallelism": f"independent shards x{ws}"},
+    }
+    if args.dump_outputs:
+        # what the last timed step left: the batch it ran on (and the flow-key records), before any
+        # later call touches them
+        a, b, d = batches[(ctr[0] - 1) % nrot]
+        dump_outputs(args.dump_outputs, rank, n, a, b, d, d_keys if fk else None, d_hash if fk else None)
+    if not args.full:
+        # a plain run ends here: set-up, warm-up, the timed steps, the line
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        for a, _, d in batches:
+            a.free()
+            d.free()
+        eng.close()
+        D.close()
+        return
 
     # kernel duration with HIP events on the launch stream (roofline), same launches
     got = None
@@ -695,31 +751,7 @@ def main():
     # one-GPU line carries the anchor that the multi-GPU lines scale
     c4_wanted = (ws == 1 and args.op == "update" and args.config == 1 and not args.packets
                  and not args.no_c4)
-    total_packets = D.sum(float(n))
-    out = {
-        "metric": ("flow keys + hash_flow per second, batched packets, MI355X" if fk else
-                   "device-resident payload GB/s checksummed, batched packets, 1/2/4/8 MI355X"
-                   + (" (fused L3 forward: TTL--, MAC rewrite, checksums)" if l3 else "")
-                   + (" (VLAN push/pop + checksums)" if args.op == "vlan" else "")),
-        "value": round(total_packets / (wall / args.steps) / 1e6, 2) if fk else
-                 round(total_frame_bytes / (wall / args.steps) / 1e9, 2),
-        "unit": "Mpkt/s" if fk else "GB/s",
-        "n_gpus": ws,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "u16 one's-complement (u8 frames, u32 word sums)",
-        "data": "synthetic (seeded generator, DESIGN.md §6), generated in HBM",
-        "config": {"workload": workload
-                   + (", fused L3 forward (next hop i % 9)" if l3 else "")
-                   + (", flow keys (header line only)" if fk else "")
-                   + (", push_vlan(100, 3) / pop_vlan() alternating, 1536-byte buffers"
-                      if args.op == "vlan" else ""),
-                   "packets_per_gpu": n, "frame_align": args.align,
-                   "frame_bytes_per_gpu": int(frame_bytes), "parallelism": f"independent shards x{ws}"},
+    out.update({
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                      "traffic": None if traffic is None else int(traffic["hbm_bytes"]),
@@ -734,7 +766,7 @@ def main():
                                          "both, their averages add up to it"),
                      "algorithmic_bytes_per_launch": int(algo_bytes), **extra_roofline},
         "parity": parity,
-    }
+    })
     if ws > 1:
         out["per_gpu_GBps"] = [round(x, 1) for x in rank_gbps]  # each rank's own rate, this run
         # each rank's own roofline: its calls timed by HIP events on its own
@@ -817,6 +849,50 @@ def main():
         d_arena.free()
     eng.close()
     D.close()
+
+
+DUMP_SAMPLE_BYTES = 40 << 20  # float32 bytes of sampled frames (or flow-key records) per dump
+DUMP_MAX_ROWS = 1 << 22      # per-packet arrays cover the batch's first 4M packets
+
+
+def dump_outputs(path: str, rank: int, n: int, d_arena, nbytes: int, d_desc, d_keys=None, d_hash=None):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as .npy files under
+    `path` (rank 0: <name>.npy, rank r > 0: <name>_rank<r>.npy), float32 unless stated, under 64 MB in
+    all. frame_index (float64) / frame_len: a sample of packets (numpy default_rng(SEED), sorted; the same
+    for the same arguments), their indexes and lengths. The update, the forward and the VLAN edit change
+    the frames in place, so their output is the batch itself:
+      frames           every byte of the sampled packets, rows zero-padded to the batch's longest frame
+      frame_byte_sums  per packet (the first 4M), the sum of its frame's bytes after the step
+    --op flowkey only reads the frames; its outputs are flow_hashes (float64, the first 4M packets) and
+    flow_records (the 64-byte records of the sampled packets)."""
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+
+    def save(name, a, dtype=np.float32):
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), np.ascontiguousarray(a, dtype=dtype))
+    desc = d_desc.download(nf.DESC_DTYPE, n)  # --op vlan updates the lengths on the device
+    off = desc["off16"].astype(np.int64) * 16
+    ln = desc["len"].astype(np.int64)
+    m = min(n, DUMP_MAX_ROWS)
+    width = max(int(ln.max()), 64)
+    k = max(1, min(n, 1 << 16 if d_keys is not None else DUMP_SAMPLE_BYTES // (4 * width)))
+    idx = np.sort(np.random.default_rng(SEED).choice(n, size=k, replace=False))
+    save("frame_index", idx, np.float64)
+    save("frame_len", ln[idx])
+    if d_keys is not None:  # the frames are only read
+        save("flow_records", d_keys.download(np.uint8, 64 * n).reshape(n, 64)[idx])
+        save("flow_hashes", d_hash.download(np.uint32, n)[:m], np.float64)  # u32: exact in float64
+        return
+    arena = d_arena.download(np.uint8, nbytes)
+    # sums of [off, off + len) per packet: reduceat over start/end pairs, the even slots (frames lie
+    # in arena order; the gaps between them land in the odd slots)
+    cuts = np.stack([off[:m], off[:m] + ln[:m]], axis=1).reshape(-1)
+    if cuts[-1] >= arena.size:
+        cuts = cuts[:-1]
+    save("frame_byte_sums", np.add.reduceat(arena, cuts, dtype=np.uint32)[::2])
+    col = np.arange(width, dtype=np.int64)
+    pos = np.minimum(off[idx, None] + col[None, :], arena.size - 1)
+    save("frames", np.where(col[None, :] < ln[idx, None], arena[pos], 0))
 
 
 def scaling_timings(D, timed, frame_bytes: float, steps: int, solo_first: bool, pre=None, after=None):
@@ -1125,11 +1201,11 @@ MORE_LINES = {
 
 
 def more_lines(args):
-    """MORE_LINES, each a child `bench.py <args> --no-cpu --no-replay --no-c4 --no-host --no-mix
+    """MORE_LINES, each a child `bench.py <args> --full --no-cpu --no-replay --no-c4 --no-host --no-mix
     --no-ops` on this GPU, summarised: its value, ms per call, roofline frac and kernel time, parity.
     A child that fails is reported as such; the default line is unaffected."""
     res = {}
-    common = ["--no-cpu", "--no-replay", "--no-c4", "--no-host", "--no-mix", "--no-ops",
+    common = ["--full", "--no-cpu", "--no-replay", "--no-c4", "--no-host", "--no-mix", "--no-ops",
               "--warmup", str(args.warmup), "--align", str(args.align)]
     for name, extra in MORE_LINES.items():
         cmd = [sys.executable, os.path.abspath(__file__), *extra, *common]
@@ -1154,12 +1230,12 @@ def host_adapter_line(n: int):
     place, pipelined); the same frames in netflow_amd::BufferPool slots of one pinned arena (no gather);
     and the reference's per-packet Packet::update_checksums() over the same PacketBuffers on 1 and on
     as many threads as the cgroup grants CPUs (16 at most) — wall clock per call, best and median of 3,
-    each result's digest against the reference's. Run by tests/cpp/_ref/netflow_adapter_test
-    `adapterbench` (compiled against the reference's headers by build(); it travels with the tree) as a
-    child process. Never `value`."""
-    exe = os.path.join(ROOT, "tests", "cpp", "_ref", "netflow_adapter_test")
+    each result's digest against the reference's. Run by oracle/_ref/netflow_adapter_test
+    `adapterbench` (compiled against the reference's headers by build()) as a child process. Never
+    `value`."""
+    exe = ADAPTER_EXE
     if not os.path.exists(exe):
-        return {"error": f"{exe} missing (built by __graft_entry__.build() where /root/reference is)"}
+        return {"error": f"{exe} missing (built by __graft_entry__.build() where the reference tree is)"}
     quota = cgroup_cpu_quota()
     threads = max(1, min(16, int(quota) if quota else len(allotted_cpus())))
     want = golden_digest(1, 0, n) or ""
@@ -1191,11 +1267,11 @@ def host_bursts_line(ring: int, sizes=BURST_SIZES, seconds: float = 0.25):
     switch.hpp:213-294) and on as many threads as the cgroup grants (16 at most); µs per call (median of
     every call in `seconds` per leg), GB/s, and the ring's digest per path against the reference's.
     `crossover_vs_reference_1_thread`: the smallest burst at which the adapter path's median call is
-    shorter than the reference's own loop over the same burst. A child process (tests/cpp/_ref/
+    shorter than the reference's own loop over the same burst. A child process (oracle/_ref/
     netflow_adapter_test burstbench), run before this process touches the GPU. Never `value`."""
-    exe = os.path.join(ROOT, "tests", "cpp", "_ref", "netflow_adapter_test")
+    exe = ADAPTER_EXE
     if not os.path.exists(exe):
-        return {"error": f"{exe} missing (built by __graft_entry__.build() where /root/reference is)"}
+        return {"error": f"{exe} missing (built by __graft_entry__.build() where the reference tree is)"}
     quota = cgroup_cpu_quota()
     threads = max(1, min(16, int(quota) if quota else len(allotted_cpus())))
     want = golden_digest(1, 0, ring) or ""

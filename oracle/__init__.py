@@ -35,12 +35,14 @@ def _ptr(a: np.ndarray, t=_u8p):
 
 
 def build(ref: bool | None = None) -> None:
-    """Compile the C restatement (and the reference shim when /root/reference exists)."""
+    """Compile the C restatement and, where the reference tree exists, oracle/_ref/: the reference
+    shim and the adapter test (which links netflow_amd/libnfcs.so: build that first)."""
     subprocess.run(["make", "-s", "-C", HERE, "all"], check=True)
     if ref is None:
         ref = os.path.isdir(os.path.join(REFERENCE_ROOT, "include", "netflow++"))
     if ref:
-        subprocess.run(["make", "-s", "-C", HERE, "ref"], check=True)
+        engine = os.path.exists(os.path.join(os.path.dirname(HERE), "netflow_amd", "libnfcs.so"))
+        subprocess.run(["make", "-s", "-C", HERE, "ref" if engine else "_ref/libnfref.so"], check=True)
 
 
 _lib = None

@@ -1,6 +1,6 @@
 // netflow_adapter_test.cpp — include/netflow_amd/netflow_adapter.hpp over NetFlow++'s OWN
 // netflow::Packet / netflow::PacketBuffer, compiled against the reference's headers
-// (/root/reference/include, by tests/cpp/Makefile into tests/cpp/_ref/, never copied into the repo).
+// (by oracle/Makefile into oracle/_ref/, never copied into the repo).
 // The reference's own Packet::update_checksums / push_vlan / pop_vlan run in this process as the
 // checker. Frames arrive as hex lines on stdin.
 //   cpu   lines "<hex>": netflow_amd::Packet::update_checksums() (the single-packet CPU path of

@@ -32,6 +32,9 @@ def test_bench_defaults():
     a = bench.make_parser().parse_args([])
     assert (a.gpus, a.config, a.packets, a.align, a.cpu_threads) == (1, 1, 0, 128, 0)
     assert not a.no_cpu and not a.no_c4 and a.op == "update"
+    # a plain run is the headline figure only: everything else waits for --full
+    assert not a.full and a.dump_outputs is None
+    assert bench.make_parser().parse_args(["--full", "--dump-outputs", "d"]).dump_outputs == "d"
 
 
 def test_cpu_baseline_reports_its_fastest_thread_count(monkeypatch):

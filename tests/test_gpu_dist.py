@@ -31,7 +31,7 @@ def test_two_ranks_one_gpu_bench_line():
     env.pop("WORLD_SIZE", None)
     env.pop("NFCS_DIST_BACKEND", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--no-cpu"]
+           "--full", "--no-cpu"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -70,7 +70,7 @@ def test_one_gpu_line_carries_c4_shard_host_and_cpu_baseline():
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2",
-           "--cpu-seconds", "1", "--no-ops"]
+           "--full", "--cpu-seconds", "1", "--no-ops"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -115,7 +115,7 @@ def test_one_gpu_line_carries_the_other_scope_lines():
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1",
-           "--no-cpu", "--no-replay", "--no-mix", "--no-host"]
+           "--full", "--no-cpu", "--no-replay", "--no-mix", "--no-host"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
@@ -131,7 +131,7 @@ def test_two_ranks_strong_split_c3():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "3", "--strong", "--steps", "3",
-           "--warmup", "1", "--no-cpu"]
+           "--warmup", "1", "--full", "--no-cpu"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

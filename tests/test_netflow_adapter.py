@@ -1,13 +1,13 @@
 """The boundary over NetFlow++'s OWN types (include/netflow_amd/netflow_adapter.hpp): a burst of
 `netflow::Packet` objects over `netflow::PacketBuffer`s — the reference's classes, compiled from its
-headers into tests/cpp/_ref/netflow_adapter_test by tests/cpp/Makefile — goes through
+headers into oracle/_ref/netflow_adapter_test by oracle/Makefile — goes through
 `netflow_amd::update_checksums_batch` / `vlan_batch` on the GPU, and the reference's own
 `Packet::update_checksums()` / `push_vlan()` / `pop_vlan()` in the same process are the checker.
 The single-packet members of netflow_amd::Packet run on the CPU (include/netflow_amd/cpu_update.hpp)
 and are checked against the reference the same way, without a GPU.
 
-The binary is built here (this container has /root/reference); on the GPU box, which does not,
-the prebuilt binary that travels with the tree is run."""
+The binary is built where the reference tree is present; elsewhere the prebuilt binary under
+oracle/_ref/ is run."""
 import json
 import os
 import subprocess
@@ -18,8 +18,8 @@ import pytest
 import oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "_ref", "netflow_adapter_test")
-REF_INCLUDE = "/root/reference/include"
+EXE = os.path.join(ROOT, "oracle", "_ref", "netflow_adapter_test")
+REF_INCLUDE = os.path.join(oracle.REFERENCE_ROOT, "include")
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -29,10 +29,10 @@ def exe():
         import netflow_amd as nf
         if not os.path.exists(nf.LIB_PATH):
             nf.build()
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp"), "ref"], check=True)
+        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "_ref/netflow_adapter_test"], check=True)
     if not os.path.exists(EXE):
         pytest.fail(f"{EXE} is missing: build it where the reference headers are "
-                    "(make -C tests/cpp ref, run by __graft_entry__.build())")
+                    "(make -C oracle ref, run by __graft_entry__.build())")
     return EXE
 
 

@@ -6,7 +6,7 @@ OUT=gpurun_out/$1; shift
 mkdir -p "$OUT"
 run() {  # name, bench args...
   local name=$1; shift
-  timeout -k 10 300 python bench.py "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"
+  timeout -k 10 300 python bench.py --full "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"
   local rc=$?
   python3 - "$OUT/bench_$name.json" "$name" <<'PY'
 import json, sys
