@@ -16,6 +16,9 @@
 //   update_checksums() switch.hpp:279-294     table_n[, status])
 //   extract_flow_key + hash_flow              netflow_amd::flow_keys_batch(pkts, keys[, hashes])
 //        packet_classifier.cpp:12-108
+//   is_my_ip, lookup_route, lookup_mac,       netflow_amd::route_lookup_batch(pkts, fib, next_hop[, egress_if,
+//   get_interface_mac  switch.hpp:259-301     verdict]) with fib = netflow_amd::make_fib(routing_manager, arp,
+//                                             if_macs, local_ips): its next hops feed l3_forward_batch
 //
 // Every entry returns 0 or a negative NFCS_E* code and never throws (the reference's calls are
 // void / bool and never throw); per-packet outcomes are the NFCS_ST_* status bytes. The bytes
@@ -30,9 +33,15 @@
 
 #include <netflow++/packet.hpp>
 
+#include <cstring>
+#include <utility>
 #include <vector>
 
 #include "netflow_amd/packet.hpp"
+
+namespace netflow {
+class RoutingManager;  // <netflow++/routing_manager.hpp>, for make_fib below
+}
 
 namespace netflow_amd {
 
@@ -67,6 +76,36 @@ inline int flow_keys_batch(netflow::Packet* const* pkts, size_t n, nfcs_flow_key
 inline int flow_keys_batch(const std::vector<netflow::Packet*>& pkts, nfcs_flow_key* keys,
                            uint32_t* hashes = nullptr) {
     return flow_keys_batch(pkts.data(), pkts.size(), keys, hashes);
+}
+
+inline int route_lookup_batch(netflow::Packet* const* pkts, size_t n, const nfcs_fib* fib, uint32_t* next_hop,
+                              uint32_t* egress_if = nullptr, uint8_t* verdict = nullptr) {
+    return detail::on_default_engine(
+        [&](ChecksumEngine& e) { return e.route_lookup_batch(pkts, n, fib, next_hop, egress_if, verdict); });
+}
+inline int route_lookup_batch(const std::vector<netflow::Packet*>& pkts, const nfcs_fib* fib, uint32_t* next_hop,
+                              uint32_t* egress_if = nullptr, uint8_t* verdict = nullptr) {
+    return route_lookup_batch(pkts.data(), pkts.size(), fib, next_hop, egress_if, verdict);
+}
+
+// A committed forwarding table (nfcs_fib) from the switch's own state: the routes are
+// RoutingManager::get_routing_table() as it is — the order lookup_route scans, which is the order
+// contract of nfcs_fib_set_routes (the reference's sort is not redone here) — plus the ARP cache
+// entries {ip, mac} (ArpProcessor keeps them in a std::map; of duplicates the last one wins), the
+// interface MACs {interface id, mac} (InterfaceManager::get_interface_mac) and the switch's own
+// addresses (InterfaceManager::is_my_ip). Returns NFCS_OK and the table in *out (nfcs_fib_destroy it;
+// upload it with ChecksumEngine::upload_fib before route_lookup_batch), or a negative NFCS_E* code.
+// A template, so that this header needs neither <netflow++/routing_manager.hpp> nor, at link time,
+// routing_manager.cpp unless make_fib is used: the caller includes that header (RoutingManager must be
+// complete where make_fib is called) and links what get_routing_table() lives in, as any user of
+// RoutingManager does. The work is netflow_amd::make_fib_from (packet.hpp), which any class with a
+// get_routing_table() of such entries can use.
+template <class RoutingManagerT = netflow::RoutingManager>
+inline int make_fib(const RoutingManagerT& rm,
+                    const std::vector<std::pair<netflow::IpAddress, netflow::MacAddress>>& arp_entries,
+                    const std::vector<std::pair<uint32_t, netflow::MacAddress>>& interface_macs,
+                    const std::vector<netflow::IpAddress>& local_ips, nfcs_fib** out) {
+    return make_fib_from(rm, arp_entries, interface_macs, local_ips, out);
 }
 
 // On an engine of the caller's (another device; one engine per GPU, one host thread each).

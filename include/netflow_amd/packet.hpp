@@ -41,6 +41,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "nfcs.h"
@@ -204,6 +205,22 @@ public:
     // the hash in .hash), hashes[i] (optional) = hash_flow(key).
     template <class Pkt>
     int flow_keys_batch(Pkt* const* pkts, size_t n, nfcs_flow_key* keys, uint32_t* hashes = nullptr);
+
+    // The switch's L3 decision in front of l3_forward_batch (switch.hpp:259-301: is_my_ip, TTL,
+    // RoutingManager::lookup_route, ArpProcessor::lookup_mac, the interface MAC) for a batch, from a
+    // committed forwarding table (nfcs_fib_*; upload_fib first): next_hop[i] = the index into the fib's
+    // next-hop table (nfcs_fib_nexthops_host) or NFCS_NH_NONE, egress_if[i] (optional) = the route's
+    // interface or NFCS_IF_NONE, verdict[i] (optional) = NFCS_RT_*. Reads the first 48 bytes of each
+    // packet and nothing more (every byte the decision reads lies below 38); the packets are not changed.
+    template <class Pkt>
+    int route_lookup_batch(Pkt* const* pkts, size_t n, const nfcs_fib* fib, uint32_t* next_hop,
+                           uint32_t* egress_if = nullptr, uint8_t* verdict = nullptr);
+    // nfcs_fib_upload to this engine's device, serialised with its other calls. The fib must be
+    // destroyed before the engine.
+    int upload_fib(nfcs_fib* fib) {
+        std::lock_guard<std::mutex> lock(mu_);
+        return nfcs_fib_upload(ctx_, fib);
+    }
 
     nfcs_ctx* ctx() const { return ctx_; }
 
@@ -533,6 +550,32 @@ int ChecksumEngine::flow_keys_batch(Pkt* const* pkts, size_t n, nfcs_flow_key* k
     return NFCS_OK;
 }
 
+template <class Pkt>
+int ChecksumEngine::route_lookup_batch(Pkt* const* pkts, size_t n, const nfcs_fib* fib, uint32_t* next_hop,
+                                       uint32_t* egress_if, uint8_t* verdict) {
+    if (n == 0) return NFCS_OK;
+    if (!pkts || !fib || !next_hop || n > 0xFFFFFFFFu) return NFCS_EINVAL;
+    std::lock_guard<std::mutex> lock(mu_);
+    // gather clamps each length to 48: the decision tests lengths against 14, 18, 34 and 38 only
+    int rc = reserve(n * 48 + 16, n);
+    if (rc) return rc;
+    const size_t off = gather(pkts, n, 48);
+    DevTmp dnh(ctx_, n * sizeof(uint32_t), rc);
+    DevTmp dif(ctx_, n * sizeof(uint32_t), rc);
+    if (rc) return rc;
+    const uint32_t m = static_cast<uint32_t>(n);
+    if ((rc = nfcs_memcpy_h2d(ctx_, d_arena_, h_arena_, off ? off : 16))) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, d_desc_, h_desc_, n * sizeof(nfcs_desc)))) return rc;
+    if ((rc = nfcs_route_lookup_device(ctx_, fib, static_cast<uint8_t*>(d_arena_), off ? off : 16,
+                                       static_cast<nfcs_desc*>(d_desc_), m, static_cast<uint32_t*>(dnh.p),
+                                       static_cast<uint32_t*>(dif.p), static_cast<uint8_t*>(d_status_), nullptr)))
+        return rc;
+    if ((rc = nfcs_memcpy_d2h(ctx_, next_hop, dnh.p, n * sizeof(uint32_t)))) return rc;
+    if (egress_if && (rc = nfcs_memcpy_d2h(ctx_, egress_if, dif.p, n * sizeof(uint32_t)))) return rc;
+    if (verdict && (rc = nfcs_memcpy_d2h(ctx_, verdict, d_status_, n))) return rc;
+    return NFCS_OK;
+}
+
 // Same interface as netflow::BufferPool (buffer_pool.hpp:57-123: allocate_buffer(payload,
 // headroom), free_buffer(buffer) with the PacketBuffer reference count), except that every
 // buffer up to slot_bytes is a slot of ONE pinned arena (nfcs_host_alloc). update_checksums_batch
@@ -734,6 +777,50 @@ inline int l3_forward_batch(Packet* const* pkts, const uint32_t* next_hop, size_
                             const nfcs_nexthop* table, uint32_t table_n, uint8_t* status = nullptr) {
     return detail::on_default_engine(
         [&](ChecksumEngine& e) { return e.l3_forward_batch(pkts, next_hop, n, table, table_n, status); });
+}
+// A committed nfcs_fib from any routing table object: rm.get_routing_table() yields entries with
+// destination_network, subnet_mask, next_hop_ip and egress_interface_id (RoutingManager's RouteEntry),
+// taken in the order given (the lookup order); arp_entries / interface_macs pair an address / interface
+// id with a MAC type that has `bytes[6]`. *out: the table (nfcs_fib_destroy it), or nullptr on error.
+template <class RoutingTable, class Mac>
+inline int make_fib_from(const RoutingTable& rm, const std::vector<std::pair<uint32_t, Mac>>& arp_entries,
+                         const std::vector<std::pair<uint32_t, Mac>>& interface_macs,
+                         const std::vector<uint32_t>& local_ips, nfcs_fib** out) {
+    if (!out) return NFCS_EINVAL;
+    *out = nullptr;
+    std::vector<nfcs_fib_route> routes;
+    for (const auto& e : rm.get_routing_table())
+        routes.push_back(nfcs_fib_route{e.destination_network, e.subnet_mask, e.next_hop_ip, e.egress_interface_id});
+    std::vector<nfcs_fib_arp> arp;
+    for (const auto& a : arp_entries) {
+        nfcs_fib_arp r{};
+        r.ip = a.first;
+        std::memcpy(r.mac, a.second.bytes, 6);
+        arp.push_back(r);
+    }
+    std::vector<nfcs_fib_if_mac> ifm;
+    for (const auto& m : interface_macs) {
+        nfcs_fib_if_mac r{};
+        r.egress_if = m.first;
+        std::memcpy(r.mac, m.second.bytes, 6);
+        ifm.push_back(r);
+    }
+    nfcs_fib* fib = nullptr;
+    int rc = nfcs_fib_create(&fib);
+    if (!rc) rc = nfcs_fib_set_routes(fib, routes.data(), static_cast<uint32_t>(routes.size()));
+    if (!rc) rc = nfcs_fib_set_arp(fib, arp.data(), static_cast<uint32_t>(arp.size()));
+    if (!rc) rc = nfcs_fib_set_if_macs(fib, ifm.data(), static_cast<uint32_t>(ifm.size()));
+    if (!rc) rc = nfcs_fib_set_local_ips(fib, local_ips.data(), static_cast<uint32_t>(local_ips.size()));
+    if (!rc) rc = nfcs_fib_commit(fib);
+    if (rc && fib) nfcs_fib_destroy(fib);
+    else *out = fib;
+    return rc;
+}
+
+inline int route_lookup_batch(Packet* const* pkts, size_t n, const nfcs_fib* fib, uint32_t* next_hop,
+                              uint32_t* egress_if = nullptr, uint8_t* verdict = nullptr) {
+    return detail::on_default_engine(
+        [&](ChecksumEngine& e) { return e.route_lookup_batch(pkts, n, fib, next_hop, egress_if, verdict); });
 }
 inline int flow_keys_batch(Packet* const* pkts, size_t n, nfcs_flow_key* keys,
                            uint32_t* hashes = nullptr) {

@@ -235,8 +235,10 @@ typedef struct nfcs_nexthop {
  * for packet i with L3 EtherType IPv4 and an IPv4 header, TTL <= 1 -> NFCS_ST_TTL_EXPIRED;
  * d_nh[i] >= table_n -> NFCS_ST_NO_ROUTE; else TTL--, dst/src MAC = d_table[d_nh[i]], then
  * Packet::update_checksums(), status = its status | NFCS_ST_FLAG_FWD. Frames that are not
- * forwarded are untouched. The control-plane steps (ACL, classification, is_my_ip, route and
- * ARP lookup) stay with the caller and arrive as next-hop indexes.
+ * forwarded are untouched. The decision in front of it (is_my_ip, route and ARP lookup) arrives as
+ * next-hop indexes: nfcs_route_lookup_device (below) computes them on the device from a nfcs_fib,
+ * whose table nfcs_fib_nexthops hands in as d_table; a caller with its own control plane may still
+ * pass any indexes into any table. ACL and classification stay with the caller.
  *   d_nh     n device-resident u32 next-hop indexes (NFCS_NH_NONE = no route)
  *   d_table  table_n device-resident next hops
  * Launches (speed only): one kernel; a burst of more than 1M long frames runs as 512K-packet
@@ -246,6 +248,113 @@ NFCS_API int nfcs_l3_forward_device(nfcs_ctx* ctx, uint8_t* d_arena, uint64_t ar
                                     const nfcs_desc* d_desc, const uint32_t* d_nh, uint32_t n,
                                     const nfcs_nexthop* d_table, uint32_t table_n,
                                     uint8_t* d_status, void* stream);
+
+/* ---- route and ARP lookup in front of the forward ----------------------------------------- */
+
+/* The symbols of this section were added without changing NFCS_ABI_VERSION (it stays 2): a caller
+ * that may meet an older library detects them by symbol lookup (dlsym "nfcs_fib_create"). */
+
+/* The switch's L3 decision for one packet (switch.hpp:259-301), in the order it is taken. */
+enum {
+    NFCS_RT_FORWARD = 0,     /* d_nh[i] = index into the FIB's next-hop table                        */
+    NFCS_RT_BAD_DESC = 1,    /* descriptor reaches outside the arena: frame not read                 */
+    NFCS_RT_NOT_IPV4 = 2,    /* the forward's predicate: len < 14, or the L3 EtherType after at most
+                                one 0x8100 tag is not 0x0800 (a tagged frame shorter than 18 keeps
+                                0x8100), or len < 34 (38 if tagged): ipv4() absent (259-269)         */
+    NFCS_RT_LOCAL = 3,       /* dst is one of the switch's own addresses (is_my_ip, 270)             */
+    NFCS_RT_TTL_EXPIRED = 4, /* TTL <= 1 (279)                                                       */
+    NFCS_RT_NO_ROUTE = 5,    /* no route entry matches (282-283, 301)                                */
+    NFCS_RT_ARP_MISS = 6,    /* the next hop (the gateway, or dst itself when next_hop_ip == 0) has
+                                no ARP entry (285-288, 300)                                          */
+    NFCS_RT_NO_IF_MAC = 7    /* the route's egress interface has no MAC (291-292)                    */
+};
+#define NFCS_IF_NONE 0xFFFFFFFFu /* d_egress_if[i] of every verdict but NFCS_RT_FORWARD */
+
+/* One route, RouteEntry without its metric (routing_manager.hpp). IPv4 addresses here and below are
+ * uint32_t in network byte order — the four address bytes as they lie in the frame, read as one
+ * u32 — which is the value of the reference's IpAddress. */
+typedef struct nfcs_fib_route {
+    uint32_t network;     /* destination_network (already masked)   */
+    uint32_t mask;        /* subnet_mask; need not be contiguous    */
+    uint32_t next_hop_ip; /* 0 = directly connected                 */
+    uint32_t egress_if;   /* egress_interface_id                    */
+} nfcs_fib_route;
+typedef struct nfcs_fib_arp {
+    uint32_t ip;
+    uint8_t mac[6];
+    uint8_t pad[2];
+} nfcs_fib_arp;
+typedef struct nfcs_fib_if_mac {
+    uint32_t egress_if;
+    uint8_t mac[6];
+    uint8_t pad[2];
+} nfcs_fib_if_mac;
+
+#define NFCS_FIB_MAX_ROUTES 4096u /* 32 KiB of {network, mask} pairs in LDS */
+
+/* The forwarding table: routes, ARP entries, interface MACs and the switch's own addresses, compiled
+ * by nfcs_fib_commit into what the lookup reads and a static next-hop table for the forward.
+ *   routes    in LOOKUP ORDER: the first entry with (dst & mask) == network wins, exactly as
+ *             RoutingManager::lookup_route scans its vector (routing_manager.cpp:80-92). The order is
+ *             taken as given — pass RoutingManager::get_routing_table() as it is. The reference's own
+ *             sort (popcount of mask, metric, network; a std::sort, so ties land in unspecified
+ *             order) is not re-implemented here. More than NFCS_FIB_MAX_ROUTES: NFCS_EINVAL.
+ *   arp       {ip, mac} in any order; of duplicates the last one wins (std::map assignment).
+ *   if_macs   {egress_if, mac}; of duplicates the last one wins.
+ *   local     the switch's own addresses (InterfaceManager::is_my_ip).
+ * Each setter copies its array (NULL with n > 0: NFCS_EINVAL) and invalidates an earlier commit:
+ * nfcs_fib_lookup_host and nfcs_fib_nexthops_host then return NFCS_EINVAL until the next
+ * nfcs_fib_commit. An earlier upload is NOT invalidated: nfcs_route_lookup_device and
+ * nfcs_fib_nexthops keep serving the tables of the last nfcs_fib_upload, so the device may run on
+ * while the host prepares the next table — and host and device answers can differ from the first
+ * setter call until the next commit AND upload. A caller that needs them equal uploads after
+ * every commit.
+ * The compiled next-hop table has one entry per distinct ARP address, then one per route with a
+ * gateway. ARP entry a serves packets whose destination is ip[a] on a connected route: every address
+ * has exactly one first-matching route, so its entry is {mac[a], if_mac(route(ip[a]).egress_if)},
+ * and unusable when that route is missing, has a gateway, or its interface has no MAC. A gateway
+ * route resolves arp(next_hop_ip) and if_mac(egress_if) once, at commit; a miss becomes the route's
+ * verdict. Unusable entries stay in the table as zeros so indexes do not shift; the lookup never
+ * hands them out. */
+typedef struct nfcs_fib nfcs_fib;
+NFCS_API int nfcs_fib_create(nfcs_fib** out);
+NFCS_API int nfcs_fib_destroy(nfcs_fib* fib); /* also frees what nfcs_fib_upload allocated */
+NFCS_API int nfcs_fib_set_routes(nfcs_fib* fib, const nfcs_fib_route* routes, uint32_t n);
+NFCS_API int nfcs_fib_set_arp(nfcs_fib* fib, const nfcs_fib_arp* arp, uint32_t n);
+NFCS_API int nfcs_fib_set_if_macs(nfcs_fib* fib, const nfcs_fib_if_mac* if_macs, uint32_t n);
+NFCS_API int nfcs_fib_set_local_ips(nfcs_fib* fib, const uint32_t* ips, uint32_t n);
+NFCS_API int nfcs_fib_commit(nfcs_fib* fib);
+/* Copies the committed tables to ctx's device (synchronous; replaces an earlier upload, which must
+ * no longer be in use). NFCS_EINVAL before nfcs_fib_commit. The fib must be destroyed before ctx. */
+NFCS_API int nfcs_fib_upload(nfcs_ctx* ctx, nfcs_fib* fib);
+/* The uploaded next-hop table, for nfcs_l3_forward_device's d_table / table_n (table_n may be 0,
+ * *d_table then NULL). NFCS_EINVAL before nfcs_fib_upload. */
+NFCS_API int nfcs_fib_nexthops(const nfcs_fib* fib, const nfcs_nexthop** d_table, uint32_t* table_n);
+/* The committed next-hop table on the host: copies min(cap, table_n) entries to `out` (may be NULL)
+ * and returns table_n through *table_n. */
+NFCS_API int nfcs_fib_nexthops_host(const nfcs_fib* fib, nfcs_nexthop* out, uint32_t cap, uint32_t* table_n);
+/* The decision for one IPv4 destination and TTL on the CPU, from the same compiled tables the
+ * kernel reads: *verdict = NFCS_RT_LOCAL .. NFCS_RT_NO_IF_MAC or NFCS_RT_FORWARD, *nh = the next-hop
+ * index or NFCS_NH_NONE, *egress_if = the route's interface or NFCS_IF_NONE (each may be NULL).
+ * NFCS_EINVAL before nfcs_fib_commit. */
+NFCS_API int nfcs_fib_lookup_host(const nfcs_fib* fib, uint32_t dst_ip, uint32_t ttl, uint32_t* verdict,
+                                  uint32_t* nh, uint32_t* egress_if);
+
+/* Batched decision of the switch's L3 path (switch.hpp:259-301) over device-resident frames: one
+ * kernel, read-only on the frames (bytes 0..47 of each at most), asynchronous on the stream.
+ *   d_nh         n u32: the next-hop index for NFCS_RT_FORWARD, NFCS_NH_NONE for every other verdict
+ *                (so nfcs_l3_forward_device leaves that frame untouched)
+ *   d_egress_if  optional (NULL) n u32: the route's egress interface, or NFCS_IF_NONE
+ *   d_verdict    optional (NULL) n bytes NFCS_RT_*
+ * fib must be uploaded to ctx (else NFCS_EINVAL) and stay unchanged until the call completes.
+ * Lookup then forward: where this verdict and the forward's status differ, the verdict is the
+ * switch's decision. The forward tests TTL before its index, so a packet to a local address with
+ * TTL 1 reads NFCS_RT_LOCAL here and NFCS_ST_TTL_EXPIRED there (the switch hands it to the CPU), and
+ * every non-forwarded IPv4 frame with TTL > 1 reads NFCS_ST_NO_ROUTE there whatever the reason here. */
+NFCS_API int nfcs_route_lookup_device(nfcs_ctx* ctx, const nfcs_fib* fib, const uint8_t* d_arena,
+                                      uint64_t arena_bytes, const nfcs_desc* d_desc, uint32_t n,
+                                      uint32_t* d_nh, uint32_t* d_egress_if, uint8_t* d_verdict,
+                                      void* stream);
 
 /* ---- VLAN push / pop + checksum ---------------------------------------- */
 

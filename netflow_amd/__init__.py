@@ -38,6 +38,14 @@ def vlan_push_op(vid: int, prio: int = 0) -> int:
     """NFCS_VLAN_PUSH_OP(vid, prio): the edit word of Packet::push_vlan(vid, prio)."""
     return VLAN_PUSH | ((prio & 7) << 13) | (vid & 0xFFF)
 
+# nfcs_route_lookup_device verdicts (include/nfcs.h NFCS_RT_*)
+RT_FORWARD, RT_BAD_DESC, RT_NOT_IPV4, RT_LOCAL, RT_TTL_EXPIRED, RT_NO_ROUTE, RT_ARP_MISS, RT_NO_IF_MAC = range(8)
+IF_NONE = 0xFFFFFFFF
+FIB_MAX_ROUTES = 4096
+FIB_ROUTE_DTYPE = np.dtype([("network", "<u4"), ("mask", "<u4"), ("next_hop_ip", "<u4"), ("egress_if", "<u4")])
+FIB_ARP_DTYPE = np.dtype([("ip", "<u4"), ("mac", "u1", (6,)), ("pad", "u1", (2,))])
+FIB_IF_MAC_DTYPE = np.dtype([("egress_if", "<u4"), ("mac", "u1", (6,)), ("pad", "u1", (2,))])
+
 NEXTHOP_DTYPE = np.dtype([("dst_mac", "u1", (6,)), ("src_mac", "u1", (6,))])
 FLOW_KEY_DTYPE = np.dtype([("hash", "<u4"), ("vlan_id", "<u2"), ("ethertype", "<u2"),
                            ("src_mac", "u1", (6,)), ("dst_mac", "u1", (6,)), ("protocol", "u1"),
@@ -124,6 +132,19 @@ def _declare(L):
         "nfcs_time_l3_forward_device": ([_vp, _vp, _u64, _vp, _vp, _u32, _vp, _u32, _vp,
                                          ctypes.c_int, _vp, ctypes.POINTER(ctypes.c_float)],
                                         ctypes.c_int),
+        "nfcs_fib_create": ([ctypes.POINTER(_vp)], ctypes.c_int),
+        "nfcs_fib_destroy": ([_vp], ctypes.c_int),
+        "nfcs_fib_set_routes": ([_vp, _vp, _u32], ctypes.c_int),
+        "nfcs_fib_set_arp": ([_vp, _vp, _u32], ctypes.c_int),
+        "nfcs_fib_set_if_macs": ([_vp, _vp, _u32], ctypes.c_int),
+        "nfcs_fib_set_local_ips": ([_vp, _vp, _u32], ctypes.c_int),
+        "nfcs_fib_commit": ([_vp], ctypes.c_int),
+        "nfcs_fib_upload": ([_vp, _vp], ctypes.c_int),
+        "nfcs_fib_nexthops": ([_vp, ctypes.POINTER(_vp), ctypes.POINTER(_u32)], ctypes.c_int),
+        "nfcs_fib_nexthops_host": ([_vp, _vp, _u32, ctypes.POINTER(_u32)], ctypes.c_int),
+        "nfcs_fib_lookup_host": ([_vp, _u32, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32),
+                                  ctypes.POINTER(_u32)], ctypes.c_int),
+        "nfcs_route_lookup_device": ([_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         # a measurement build of an earlier round (NFCS_LIB, A/B runs) may lack a later entry point;
@@ -174,6 +195,93 @@ def shard_bytes(desc: np.ndarray, parts: int) -> np.ndarray:
     _check(lib().nfcs_shard_bytes(desc.ctypes.data if len(desc) else None, len(desc), parts,
                                   bounds.ctypes.data), "nfcs_shard_bytes")
     return bounds
+
+
+def ip4(a: str) -> int:
+    """A dotted IPv4 address as the u32 the tables and frames hold: network byte order, i.e. the four
+    address bytes in frame order read as one little-endian u32 (the reference's IpAddress)."""
+    return int.from_bytes(bytes(int(x) for x in a.split(".")), "little")
+
+
+class Fib:
+    """The forwarding table behind Engine.route_lookup_device (nfcs_fib): routes in lookup order (the
+    first match wins: pass RoutingManager::get_routing_table() as it is), ARP entries, interface MACs
+    and the switch's own addresses. Addresses are u32 in network byte order (ip4())."""
+
+    def __init__(self):
+        p = _vp()
+        _check(lib().nfcs_fib_create(ctypes.byref(p)), "nfcs_fib_create")
+        self.ptr = p.value
+
+    def _set(self, fn, arr, dtype):
+        arr = np.ascontiguousarray(arr, dtype=dtype)
+        _check(getattr(lib(), fn)(self.ptr, arr.ctypes.data if len(arr) else None, len(arr)), fn)
+        return self
+
+    def set_routes(self, routes):
+        """FIB_ROUTE_DTYPE records {network, mask, next_hop_ip, egress_if}, in lookup order."""
+        return self._set("nfcs_fib_set_routes", routes, FIB_ROUTE_DTYPE)
+
+    def set_arp(self, arp):
+        """FIB_ARP_DTYPE records {ip, mac}; of duplicates the last one wins."""
+        return self._set("nfcs_fib_set_arp", arp, FIB_ARP_DTYPE)
+
+    def set_if_macs(self, if_macs):
+        """FIB_IF_MAC_DTYPE records {egress_if, mac}."""
+        return self._set("nfcs_fib_set_if_macs", if_macs, FIB_IF_MAC_DTYPE)
+
+    def set_local_ips(self, ips):
+        return self._set("nfcs_fib_set_local_ips", ips, np.dtype("<u4"))
+
+    def commit(self):
+        _check(lib().nfcs_fib_commit(self.ptr), "nfcs_fib_commit")
+        return self
+
+    def upload(self, engine: "Engine"):
+        """Copy the committed tables to the engine's device; close the Fib before the engine."""
+        _check(lib().nfcs_fib_upload(engine.ctx, self.ptr), "nfcs_fib_upload")
+        return self
+
+    def nexthops(self) -> tuple[int, int]:
+        """(device pointer, entries) of the uploaded next-hop table, for l3_forward_device."""
+        p, n = _vp(), _u32()
+        _check(lib().nfcs_fib_nexthops(self.ptr, ctypes.byref(p), ctypes.byref(n)), "nfcs_fib_nexthops")
+        return p.value or 0, int(n.value)
+
+    def nexthops_host(self) -> np.ndarray:
+        """The committed next-hop table as NEXTHOP_DTYPE records."""
+        n = _u32()
+        _check(lib().nfcs_fib_nexthops_host(self.ptr, None, 0, ctypes.byref(n)), "nfcs_fib_nexthops_host")
+        out = np.zeros(n.value, dtype=NEXTHOP_DTYPE)
+        if n.value:
+            _check(lib().nfcs_fib_nexthops_host(self.ptr, out.ctypes.data, n.value, ctypes.byref(n)),
+                   "nfcs_fib_nexthops_host")
+        return out
+
+    def lookup_host(self, dst_ip: int, ttl: int) -> tuple[int, int, int]:
+        """(verdict, next-hop index, egress interface) for one destination and TTL, on the CPU, from
+        the tables the kernel reads (nfcs_fib_lookup_host)."""
+        v, h, e = _u32(), _u32(), _u32()
+        _check(lib().nfcs_fib_lookup_host(self.ptr, int(dst_ip), int(ttl), ctypes.byref(v), ctypes.byref(h),
+                                          ctypes.byref(e)), "nfcs_fib_lookup_host")
+        return int(v.value), int(h.value), int(e.value)
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            lib().nfcs_fib_destroy(self.ptr)
+            self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DeviceBuffer:
@@ -337,6 +445,15 @@ class Engine:
         _check(lib().nfcs_l3_forward_device(self.ctx, ptr(arena), arena_bytes, ptr(desc), ptr(nh), n,
                                             ptr(table), table_n, ptr(status), stream),
                "nfcs_l3_forward_device")
+
+    def route_lookup_device(self, fib: Fib, arena, arena_bytes: int, desc, n: int, nh, egress_if=None,
+                            verdict=None, stream=None):
+        """The switch's L3 decision per frame (is_my_ip, TTL, route, ARP, interface MAC) on device
+        frames, read-only: nh = n u32 next-hop indexes into fib.nexthops() (NH_NONE unless the verdict
+        is RT_FORWARD), ready for l3_forward_device; egress_if (n u32) and verdict (n bytes RT_*) optional."""
+        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
+        _check(lib().nfcs_route_lookup_device(self.ctx, fib.ptr, ptr(arena), arena_bytes, ptr(desc), n, ptr(nh),
+                                              ptr(egress_if), ptr(verdict), stream), "nfcs_route_lookup_device")
 
     def vlan_device(self, arena, arena_bytes: int, desc, n: int, ops=None, op_all: int = 0,
                     caps=None, cap_all: int = 0, status=None, stream=None):

@@ -965,6 +965,167 @@ NFCS_API int nfcs_flow_keys_device(nfcs_ctx* c, const uint8_t* d_arena, uint64_t
     return NFCS_OK;
 }
 
+// ---- forwarding table (nfcs_fib.h: inputs, commit, host decision) and its lookup kernel ----------
+}  // extern "C"
+
+struct nfcs_fib {
+    nfcs::FibInputs in;
+    nfcs::FibTables t;
+    bool committed = false;
+    // nfcs_fib_upload: one device allocation holding every array, on `device`
+    int device = -1;
+    uint8_t* d_blob = nullptr;
+    nfcs::FibDev dev;
+    const nfcs_nexthop* d_table = nullptr;
+    uint32_t d_table_n = 0;  // the table as uploaded (a later commit does not change it)
+    bool uploaded = false;
+};
+
+namespace {
+void fib_drop_upload(nfcs_fib* f) {
+    if (f->d_blob) {
+        DeviceGuard dg_(f->device);
+        if (dg_.err == hipSuccess) (void)hipFree(f->d_blob);
+    }
+    f->d_blob = nullptr;
+    f->dev = nfcs::FibDev{};
+    f->d_table = nullptr;
+    f->d_table_n = 0;
+    f->uploaded = false;
+}
+template <class T>
+int fib_set(nfcs_fib* f, std::vector<T>& dst, const T* src, uint32_t n) {
+    if (!f || (n > 0 && !src)) return NFCS_EINVAL;
+    try {
+        dst.assign(src, src + n);
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+    f->committed = false;  // the device copy, if any, stays as it is until the next upload
+    return NFCS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+NFCS_API int nfcs_fib_create(nfcs_fib** out) {
+    if (!out) return NFCS_EINVAL;
+    *out = new (std::nothrow) nfcs_fib();
+    return *out ? NFCS_OK : NFCS_ENOMEM;
+}
+
+NFCS_API int nfcs_fib_destroy(nfcs_fib* f) {
+    if (!f) return NFCS_EINVAL;
+    fib_drop_upload(f);
+    delete f;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_fib_set_routes(nfcs_fib* f, const nfcs_fib_route* routes, uint32_t n) {
+    if (n > NFCS_FIB_MAX_ROUTES) return NFCS_EINVAL;
+    return f ? fib_set(f, f->in.routes, routes, n) : NFCS_EINVAL;
+}
+NFCS_API int nfcs_fib_set_arp(nfcs_fib* f, const nfcs_fib_arp* arp, uint32_t n) {
+    return f ? fib_set(f, f->in.arp, arp, n) : NFCS_EINVAL;
+}
+NFCS_API int nfcs_fib_set_if_macs(nfcs_fib* f, const nfcs_fib_if_mac* if_macs, uint32_t n) {
+    return f ? fib_set(f, f->in.if_macs, if_macs, n) : NFCS_EINVAL;
+}
+NFCS_API int nfcs_fib_set_local_ips(nfcs_fib* f, const uint32_t* ips, uint32_t n) {
+    return f ? fib_set(f, f->in.local_ips, ips, n) : NFCS_EINVAL;
+}
+
+NFCS_API int nfcs_fib_commit(nfcs_fib* f) {
+    if (!f) return NFCS_EINVAL;
+    try {
+        nfcs::fib_compile(f->in, f->t);
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+    f->committed = true;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_fib_upload(nfcs_ctx* c, nfcs_fib* f) {
+    if (!c || !f || !f->committed) return NFCS_EINVAL;
+    fib_drop_upload(f);
+    DeviceGuard dg_(c->di.device);
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    const nfcs::FibTables& t = f->t;
+    // one blob, every array on a 16-byte boundary
+    auto up16 = [](size_t x) { return (x + 15u) & ~size_t(15); };
+    const size_t o_nm = 0, o_info = o_nm + up16(t.rt_nm.size() * 8u), o_aip = o_info + up16(t.rt_info.size() * 8u);
+    const size_t o_anh = o_aip + up16(t.arp_ip.size() * 4u), o_loc = o_anh + up16(t.arp_nh.size() * 4u);
+    const size_t o_tab = o_loc + up16(t.local_ip.size() * 4u), total = o_tab + up16(t.table.size() * sizeof(nfcs_nexthop));
+    std::vector<uint8_t> blob(total + 16u, 0);
+    auto put = [&](size_t o, const void* p, size_t bytes) {
+        if (bytes) memcpy(blob.data() + o, p, bytes);
+    };
+    put(o_nm, t.rt_nm.data(), t.rt_nm.size() * 8u);
+    put(o_info, t.rt_info.data(), t.rt_info.size() * 8u);
+    put(o_aip, t.arp_ip.data(), t.arp_ip.size() * 4u);
+    put(o_anh, t.arp_nh.data(), t.arp_nh.size() * 4u);
+    put(o_loc, t.local_ip.data(), t.local_ip.size() * 4u);
+    put(o_tab, t.table.data(), t.table.size() * sizeof(nfcs_nexthop));
+    NFCS_HIP(hipMalloc(&f->d_blob, blob.size()));
+    f->device = c->di.device;
+    const hipError_t e = hipMemcpy(f->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        fib_drop_upload(f);
+        return hip_fail(e);
+    }
+    f->dev.rt_nm = (const uint2*)(f->d_blob + o_nm);
+    f->dev.rt_info = (const uint2*)(f->d_blob + o_info);
+    f->dev.routes = t.routes;
+    f->dev.routes_padded = (uint32_t)t.rt_nm.size();
+    f->dev.arp_ip = (const uint32_t*)(f->d_blob + o_aip);
+    f->dev.arp_nh = (const uint32_t*)(f->d_blob + o_anh);
+    f->dev.arps = (uint32_t)t.arp_ip.size();
+    f->dev.local_ip = (const uint32_t*)(f->d_blob + o_loc);
+    f->dev.locals = (uint32_t)t.local_ip.size();
+    f->d_table = t.table.empty() ? nullptr : (const nfcs_nexthop*)(f->d_blob + o_tab);
+    f->d_table_n = (uint32_t)t.table.size();
+    f->uploaded = true;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_fib_nexthops(const nfcs_fib* f, const nfcs_nexthop** d_table, uint32_t* table_n) {
+    if (!f || !f->uploaded || !d_table || !table_n) return NFCS_EINVAL;
+    *d_table = f->d_table;
+    *table_n = f->d_table_n;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_fib_nexthops_host(const nfcs_fib* f, nfcs_nexthop* out, uint32_t cap, uint32_t* table_n) {
+    if (!f || !f->committed || !table_n) return NFCS_EINVAL;
+    const uint32_t tn = (uint32_t)f->t.table.size();
+    if (out && cap && tn) memcpy(out, f->t.table.data(), sizeof(nfcs_nexthop) * (cap < tn ? cap : tn));
+    *table_n = tn;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_fib_lookup_host(const nfcs_fib* f, uint32_t dst_ip, uint32_t ttl, uint32_t* verdict,
+                                  uint32_t* nh, uint32_t* egress_if) {
+    if (!f || !f->committed) return NFCS_EINVAL;
+    nfcs::fib_decide(f->t, dst_ip, ttl, verdict, nh, egress_if);
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_route_lookup_device(nfcs_ctx* c, const nfcs_fib* f, const uint8_t* d_arena,
+                                      uint64_t arena_bytes, const nfcs_desc* d_desc, uint32_t n,
+                                      uint32_t* d_nh, uint32_t* d_egress_if, uint8_t* d_verdict,
+                                      void* stream) {
+    if (!c || !f || !f->uploaded || f->device != c->di.device) return NFCS_EINVAL;
+    DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    if (n == 0) return NFCS_OK;
+    if (!d_arena || !d_desc || !d_nh || ((uintptr_t)d_arena & 15u)) return NFCS_EINVAL;
+    if (((uintptr_t)d_nh & 3u) || ((uintptr_t)d_egress_if & 3u)) return NFCS_EINVAL;
+    NFCS_HIP(nfcs::launch_route_lookup(c->di, f->dev, d_arena, arena_bytes, d_desc, n, d_nh, d_egress_if,
+                                       d_verdict, pick(c, stream)));
+    return NFCS_OK;
+}
+
 NFCS_API int nfcs_update_host(nfcs_ctx* c, uint8_t* h_arena, uint64_t arena_bytes,
                               const nfcs_desc* h_desc, uint32_t n, uint8_t* h_status,
                               uint32_t flags) {

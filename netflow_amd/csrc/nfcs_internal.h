@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "nfcs.h"
+#include "nfcs_fib.h"
 
 namespace nfcs {
 
@@ -182,6 +183,22 @@ hipError_t launch_vlan(const DevInfo& di, uint8_t* arena, uint64_t arena_bytes, 
 hipError_t launch_flow_keys(const DevInfo& di, const uint8_t* arena, uint64_t arena_bytes,
                             const nfcs_desc* desc, uint32_t n, nfcs_flow_key* keys,
                             uint32_t* hashes, hipStream_t stream);
+
+// The committed forwarding table in device memory (nfcs_fib_upload; the arrays of FibTables, nfcs_fib.h).
+struct FibDev {
+    const uint2* rt_nm = nullptr;    // routes_padded {network, mask} pairs, 16-byte aligned
+    const uint2* rt_info = nullptr;  // routes {next-hop index or kRt* code, egress_if}
+    uint32_t routes = 0, routes_padded = 0;
+    const uint32_t* arp_ip = nullptr;  // arps ascending addresses
+    const uint32_t* arp_nh = nullptr;  // per address: next-hop index or NFCS_NH_NONE
+    uint32_t arps = 0;
+    const uint32_t* local_ip = nullptr;  // locals ascending addresses
+    uint32_t locals = 0;
+};
+
+hipError_t launch_route_lookup(const DevInfo& di, const FibDev& fib, const uint8_t* arena, uint64_t arena_bytes,
+                               const nfcs_desc* desc, uint32_t n, uint32_t* nh, uint32_t* egress_if,
+                               uint8_t* verdict, hipStream_t stream);
 
 hipError_t launch_gen_config(const DevInfo& di, int config, uint64_t seed, uint64_t first,
                              uint32_t n, uint8_t* arena, uint64_t arena_bytes,

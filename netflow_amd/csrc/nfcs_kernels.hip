@@ -2074,6 +2074,153 @@ hipError_t launch_flow_keys(const DevInfo& di, const uint8_t* arena, uint64_t ar
     return hipGetLastError();
 }
 
+// ---- route + ARP lookup in front of the fused forward -------------------------
+// The switch's L3 decision (switch.hpp:259-301) per packet, in flow_keys_lanes_kernel's shape: a wave
+// takes 64 packets, loads header bytes 0..47 (every byte the decision reads lies below 38) in 8-lane
+// rows, one line per packet, and lane l decides packet l from LDS. The {network, mask} pairs of the
+// routes are staged once per workgroup in LDS behind the header rows and scanned in lookup order by
+// a wave-uniform loop: every lane reads the same pair (an LDS broadcast, no bank conflict), kRtGroup
+// pairs per trip, and the wave leaves the loop once each of its lanes has its first match
+// (RoutingManager::lookup_route, routing_manager.cpp:80-92). ARP entries and the switch's own
+// addresses are ascending u32 arrays in global memory, searched per lane.
+constexpr uint32_t kRtRow = 48;  // LDS bytes per packet: header bytes 0..47
+constexpr uint32_t kRtRowsBytes = kWavesPerBlock * 64u * kRtRow;
+
+DEV uint32_t dev_find(const uint32_t* __restrict__ a, uint32_t n, uint32_t key) {  // nfcs_fib.h fib_find
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (a[mid] < key) lo = mid + 1u;
+        else hi = mid;
+    }
+    return (lo < n && a[lo] == key) ? lo : NFCS_NH_NONE;
+}
+
+__global__ __launch_bounds__(kBlock) void route_lookup_kernel(const nfcs_desc* __restrict__ desc, uint32_t n,
+                                                              uint32_t nblocks, const uint8_t* __restrict__ arena,
+                                                              uint64_t arena_bytes, const FibDev fib,
+                                                              uint32_t* __restrict__ nh_out,
+                                                              uint32_t* __restrict__ if_out,
+                                                              uint8_t* __restrict__ verdict_out) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t rt_lds[];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t p0 = ((uint64_t)xcd_block_n(nblocks) * kWavesPerBlock + rfl(wave)) * 64u;
+    uint8_t* rows = rt_lds + wave * 64u * kRtRow;
+    // lane l: descriptor of packet p0 + l (one coalesced load); dead packets read as length 0
+    const uint64_t p = p0 + lane;
+    uint2 dl = make_uint2(0u, 0u);
+    if (p < n) dl = ((const uint2*)desc)[p];
+    const uint64_t off = (uint64_t)dl.x * 16u;
+    const bool live = p < n && off + (((uint64_t)dl.y + 15u) & ~15ull) <= arena_bytes;
+    const uint32_t len = live ? dl.y : 0u;
+    // header chunks 0..2 in 8-lane rows (instruction k, row r -> packet 8k + r, lane rl -> chunk rl),
+    // non-temporal: the frames are read once
+    const uint32_t rl = lane & 7u, r = lane >> 3;
+    const uint4* zl = g_zero_line;
+    uint4 c[8];
+    if (p0 < n) {
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) {
+            const uint32_t q = 8u * k + r;
+            const uint32_t qo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)dl.x);
+            const uint32_t ql = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)len);
+            const uint4* src = (const uint4*)(arena + (uint64_t)qo * 16u);
+            c[k] = ld16<1>((rl < 3u && rl * 16u < ql) ? src + rl : zl);
+        }
+    }
+    // the routes' {network, mask} pairs, two per 16-byte piece, once per workgroup (every wave of the
+    // workgroup takes part, also one past n: it leaves after the barrier)
+    uint4* rt4 = (uint4*)(rt_lds + kRtRowsBytes);
+    const uint32_t n4 = fib.routes_padded / 2u;
+    for (uint32_t i0 = 0; i0 < n4; i0 += 4u * kBlock) {  // 4 loads in flight per lane (index clamped, not branched)
+        uint4 t[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t i = i0 + j * kBlock + threadIdx.x;
+            t[j] = ((const uint4*)fib.rt_nm)[i < n4 ? i : n4 - 1u];
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t i = i0 + j * kBlock + threadIdx.x;
+            if (i < n4) rt4[i] = t[j];
+        }
+    }
+    __syncthreads();
+    if (p0 >= n) return;
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k)
+        if (rl < 3u) *(uint4*)(rows + (8u * k + r) * kRtRow + 16u * rl) = c[k];
+    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes are done
+    __builtin_amdgcn_wave_barrier();
+    // lane l decides packet l. The forward's predicate (row_process above): L3 EtherType after at
+    // most one tag, ipv4() present
+    const uint8_t* b = rows + lane * kRtRow;
+    const uint32_t e12 = lds_be16(b, 12);
+    const bool tagged = e12 == 0x8100u;
+    const uint32_t l3t = len < 14 ? 0u : (tagged ? (len >= 18 ? lds_be16(b, 16) : e12) : e12);
+    const bool v4 = live && l3t == 0x0800u && (tagged ? 38u : 34u) <= len;
+    const uint32_t sh = tagged ? 4u : 0u;
+    const uint32_t ttl = lds_u8(b, 22u + sh);
+    const uint32_t dst = lds_le32(b, 30u + sh);  // network byte order as a u32: the reference's IpAddress
+    const bool local = v4 && dev_find(fib.local_ip, fib.locals, dst) != NFCS_NH_NONE;  // is_my_ip (270)
+    const bool need = v4 && !local && ttl > 1;  // lookup_route runs (282)
+    const uint2* rt = (const uint2*)(rt_lds + kRtRowsBytes);
+    uint32_t match = NFCS_NH_NONE;
+    for (uint32_t i = 0; i < fib.routes_padded; i += kRtGroup) {
+        if (__builtin_amdgcn_ballot_w64(need && match == NFCS_NH_NONE) == 0) break;
+        uint32_t m = NFCS_NH_NONE;
+#pragma unroll
+        for (uint32_t j = kRtGroup; j-- > 0;) {  // descending, so the first pair in order wins
+            const uint2 e = rt[i + j];
+            m = ((dst & e.y) == e.x) ? i + j : m;
+        }
+        match = match == NFCS_NH_NONE ? m : match;
+    }
+    uint32_t v = !live ? (uint32_t)NFCS_RT_BAD_DESC
+               : !v4   ? (uint32_t)NFCS_RT_NOT_IPV4
+               : local ? (uint32_t)NFCS_RT_LOCAL
+                       : (uint32_t)NFCS_RT_TTL_EXPIRED;
+    uint32_t nh = NFCS_NH_NONE, eif = NFCS_IF_NONE;
+    if (need) {
+        v = NFCS_RT_NO_ROUTE;
+        if (match != NFCS_NH_NONE) {  // match < fib.routes: the padding pairs match nothing
+            const uint2 info = fib.rt_info[match];
+            if (info.x == kRtGwArpMiss) v = NFCS_RT_ARP_MISS;
+            else if (info.x == kRtGwNoIfMac) v = NFCS_RT_NO_IF_MAC;
+            else if (info.x == kRtConnected) {  // ARP for the destination itself (285-286)
+                const uint32_t a = dev_find(fib.arp_ip, fib.arps, dst);
+                if (a == NFCS_NH_NONE) v = NFCS_RT_ARP_MISS;
+                else {
+                    nh = fib.arp_nh[a];
+                    v = nh == NFCS_NH_NONE ? (uint32_t)NFCS_RT_NO_IF_MAC : (uint32_t)NFCS_RT_FORWARD;
+                }
+            } else {
+                nh = info.x;
+                v = NFCS_RT_FORWARD;
+            }
+            if (v == NFCS_RT_FORWARD) eif = info.y;
+        }
+    }
+    if (p < n) {  // one packet per lane: each store instruction writes consecutive elements
+        nh_out[p] = nh;
+        if (if_out) if_out[p] = eif;
+        if (verdict_out) verdict_out[p] = (uint8_t)v;
+    }
+}
+
+hipError_t launch_route_lookup(const DevInfo& di, const FibDev& fib, const uint8_t* arena, uint64_t arena_bytes,
+                               const nfcs_desc* desc, uint32_t n, uint32_t* nh, uint32_t* egress_if,
+                               uint8_t* verdict, hipStream_t stream) {
+    (void)di;
+    if (n == 0) return hipSuccess;
+    // 64 packets per wave, one lane each, XCD-aware order; LDS: the header rows, then the pairs
+    const uint32_t g = (n + 255u) / 256u;
+    const unsigned lds = kRtRowsBytes + fib.routes_padded * 8u;
+    hipLaunchKernelGGL(route_lookup_kernel, dim3(g), dim3(kBlock), lds, stream, desc, n, g, arena, arena_bytes, fib,
+                       nh, egress_if, verdict);
+    return hipGetLastError();
+}
+
 // ---- synthetic config generator (same spec as oracle/nfcs_oracle.c) -----------
 constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
 __host__ __device__ inline uint64_t mix64(uint64_t z) {
