@@ -19,6 +19,9 @@
 //   is_my_ip, lookup_route, lookup_mac,       netflow_amd::route_lookup_batch(pkts, fib, next_hop[, egress_if,
 //   get_interface_mac  switch.hpp:259-301     verdict]) with fib = netflow_amd::make_fib(routing_manager, arp,
 //                                             if_macs, local_ips): its next hops feed l3_forward_batch
+//   AclManager::evaluate                      netflow_amd::acl_eval_batch(pkts, acl, action[, rule_index,
+//        acl_manager.cpp:161-278              redirect_port, next_hop]) with acl = netflow_amd::make_acl(
+//                                             acl_manager.get_all_rules(name)): masks next_hop for l3_forward_batch
 //
 // Every entry returns 0 or a negative NFCS_E* code and never throws (the reference's calls are
 // void / bool and never throw); per-packet outcomes are the NFCS_ST_* status bytes. The bytes
@@ -41,6 +44,7 @@
 
 namespace netflow {
 class RoutingManager;  // <netflow++/routing_manager.hpp>, for make_fib below
+struct AclRule;        // <netflow++/acl_manager.hpp>, for make_acl below
 }
 
 namespace netflow_amd {
@@ -106,6 +110,32 @@ inline int make_fib(const RoutingManagerT& rm,
                     const std::vector<std::pair<uint32_t, netflow::MacAddress>>& interface_macs,
                     const std::vector<netflow::IpAddress>& local_ips, nfcs_fib** out) {
     return make_fib_from(rm, arp_entries, interface_macs, local_ips, out);
+}
+
+inline int acl_eval_batch(netflow::Packet* const* pkts, size_t n, const nfcs_acl* acl, uint8_t* action,
+                          uint32_t* rule_index = nullptr, uint32_t* redirect_port = nullptr,
+                          uint32_t* next_hop = nullptr) {
+    return detail::on_default_engine(
+        [&](ChecksumEngine& e) { return e.acl_eval_batch(pkts, n, acl, action, rule_index, redirect_port, next_hop); });
+}
+inline int acl_eval_batch(const std::vector<netflow::Packet*>& pkts, const nfcs_acl* acl, uint8_t* action,
+                          uint32_t* rule_index = nullptr, uint32_t* redirect_port = nullptr,
+                          uint32_t* next_hop = nullptr) {
+    return acl_eval_batch(pkts.data(), pkts.size(), acl, action, rule_index, redirect_port, next_hop);
+}
+
+// A committed rule list (nfcs_acl) from one of the switch's named ACLs: AclManager::get_all_rules(name)
+// as it is — the order evaluate walks, compiled or not, which is the order contract of
+// nfcs_acl_set_rules (compile_rules' sort is not redone here). Each engaged std::optional of a rule
+// becomes its NFCS_ACL_F_* bit, the addresses stay in host byte order as AclRule holds them, and the
+// address masks are full (the reference matches addresses exactly). Returns NFCS_OK and the list in *out
+// (nfcs_acl_destroy it; upload it with ChecksumEngine::upload_acl before acl_eval_batch), or a negative
+// NFCS_E* code. A template, so that this header does not need <netflow++/acl_manager.hpp> unless
+// make_acl is used: the caller includes it (AclRule must be complete where make_acl is called). The work
+// is netflow_amd::make_acl_from (packet.hpp), which any rule struct with AclRule's members can use.
+template <class AclRuleT = netflow::AclRule>
+inline int make_acl(const std::vector<AclRuleT>& rules, nfcs_acl** out) {
+    return make_acl_from(rules, out);
 }
 
 // On an engine of the caller's (another device; one engine per GPU, one host thread each).

@@ -238,7 +238,10 @@ typedef struct nfcs_nexthop {
  * forwarded are untouched. The decision in front of it (is_my_ip, route and ARP lookup) arrives as
  * next-hop indexes: nfcs_route_lookup_device (below) computes them on the device from a nfcs_fib,
  * whose table nfcs_fib_nexthops hands in as d_table; a caller with its own control plane may still
- * pass any indexes into any table. ACL and classification stay with the caller.
+ * pass any indexes into any table. The ACL in front of both is nfcs_acl_eval_device (further
+ * below): run between the lookup and the forward it sets d_nh[i] = NFCS_NH_NONE for every packet
+ * the ingress ACL does not permit, so this call leaves that frame untouched. Classification stays
+ * with the caller (nfcs_flow_keys_device computes its keys).
  *   d_nh     n device-resident u32 next-hop indexes (NFCS_NH_NONE = no route)
  *   d_table  table_n device-resident next hops
  * Launches (speed only): one kernel; a burst of more than 1M long frames runs as 512K-packet
@@ -355,6 +358,122 @@ NFCS_API int nfcs_route_lookup_device(nfcs_ctx* ctx, const nfcs_fib* fib, const 
                                       uint64_t arena_bytes, const nfcs_desc* d_desc, uint32_t n,
                                       uint32_t* d_nh, uint32_t* d_egress_if, uint8_t* d_verdict,
                                       void* stream);
+
+/* ---- ACL evaluation in front of the route lookup and the forward --------------------------- */
+
+/* AclManager::evaluate (acl_manager.cpp:161-278) for a batch of device-resident frames: the first
+ * step of process_received_packet (switch.hpp:219-245, the ingress port's ACL) and the last of
+ * process_egress_pipeline (the egress ACL). The symbols of this section were added without changing
+ * NFCS_ABI_VERSION (it stays 2): detect them by symbol lookup (dlsym "nfcs_acl_create"). */
+
+/* The decision per packet: the values of the reference's AclActionType, and one of this library's. */
+#define NFCS_ACL_PERMIT 0u   /* a PERMIT rule matched first, or no rule matched (the default)       */
+#define NFCS_ACL_DENY 1u     /* a DENY rule matched first, or a REDIRECT rule WITHOUT a port did    */
+#define NFCS_ACL_REDIRECT 2u /* a REDIRECT rule with a port matched first                            */
+#define NFCS_ACL_BAD_DESC 3u /* the descriptor reaches outside the arena: the frame is not read      */
+
+#define NFCS_ACL_NO_MATCH 0xFFFFFFFFu /* d_rule[i] when no rule matched (or NFCS_ACL_BAD_DESC)       */
+#define NFCS_ACL_MAX_RULES 512u       /* 32 KiB of compiled rules in LDS                             */
+
+/* nfcs_acl_rule.fields: which match fields the rule sets (AclRule's engaged std::optionals). A field
+ * whose bit is clear is a wildcard and its value is ignored. */
+#define NFCS_ACL_F_SRC_MAC 0x001u
+#define NFCS_ACL_F_DST_MAC 0x002u
+#define NFCS_ACL_F_VLAN_ID 0x004u
+#define NFCS_ACL_F_ETHERTYPE 0x008u
+#define NFCS_ACL_F_SRC_IP 0x010u
+#define NFCS_ACL_F_DST_IP 0x020u
+#define NFCS_ACL_F_PROTOCOL 0x040u
+#define NFCS_ACL_F_SRC_PORT 0x080u
+#define NFCS_ACL_F_DST_PORT 0x100u
+#define NFCS_ACL_F_ALL 0x1FFu
+
+/* One rule, AclRule (acl_manager.hpp:28-69) without its priority.
+ *
+ * !!! BYTE ORDER: src_ip, dst_ip and their masks are in HOST byte order (10.1.2.3 = 0x0A010203), as
+ * !!! AclRule holds them (check_match compares ntohl(header field) with them). This is the OPPOSITE
+ * !!! of nfcs_fib_route / nfcs_fib_arp above, whose addresses are in NETWORK byte order like the
+ * !!! reference's IpAddress. vlan_id, ethertype and the ports are host-order numbers as well.
+ *
+ * src_ip_mask / dst_ip_mask extend the reference (its own TODO, acl_manager.hpp:48): the address
+ * matches when (ntohl(packet address) & mask) == (rule address & mask). 0xFFFFFFFF is the
+ * reference's exact match; a mask of 0 matches every address but still needs an IPv4 header. */
+typedef struct nfcs_acl_rule {
+    uint32_t fields;        /* NFCS_ACL_F_* bits; any other bit: NFCS_EINVAL                        */
+    uint32_t rule_id;       /* informational only: the decision reports the rule's INDEX in the list */
+    uint8_t src_mac[6];
+    uint8_t dst_mac[6];
+    uint16_t vlan_id;       /* compared with TCI & 0x0FFF                                            */
+    uint16_t ethertype;     /* compared with the EtherType after at most one 0x8100 tag              */
+    uint32_t src_ip;        /* HOST byte order                                                       */
+    uint32_t dst_ip;        /* HOST byte order                                                       */
+    uint32_t src_ip_mask;   /* HOST byte order; 0xFFFFFFFF = exact                                   */
+    uint32_t dst_ip_mask;
+    uint16_t src_port;
+    uint16_t dst_port;
+    uint8_t protocol;
+    uint8_t action;         /* NFCS_ACL_PERMIT / DENY / REDIRECT; anything else: NFCS_EINVAL         */
+    uint8_t pad[2];
+    uint32_t redirect_port; /* redirect_port_id, NFCS_IF_NONE = absent (REDIRECT then decides DENY)  */
+} nfcs_acl_rule;
+#ifdef __cplusplus
+static_assert(sizeof(nfcs_acl_rule) == 52, "nfcs_acl_rule is a 52-byte record");
+#endif
+
+/* One rule list (one named ACL of AclManager).
+ *   rules   scanned IN THE ORDER GIVEN: the first rule whose check_match holds decides, exactly as
+ *           AclManager::evaluate walks its vector — compiled or not. Pass get_all_rules(name) as it
+ *           is; compile_rules' sort (priority descending, then rule id) is not redone here. No rule
+ *           matching: NFCS_ACL_PERMIT. A REDIRECT rule without a port decides NFCS_ACL_DENY at that
+ *           rule (the scan stops there). More than NFCS_ACL_MAX_RULES: NFCS_EINVAL. An empty list is
+ *           valid: every frame is permitted.
+ * check_match per rule over a frame of len bytes: the MACs need len >= 14; vlan_id needs an 0x8100 tag
+ * and len >= 18; the EtherType is bytes 12-13, or 16-17 behind a tag with len >= 18, and is unknown
+ * otherwise — a rule that sets any of ethertype / src_ip / dst_ip / protocol / the ports then fails,
+ * a rule that sets none of them can still match (a rule without fields matches every frame, a 10-byte
+ * one included). Any of src_ip / dst_ip / protocol / the ports needs EtherType 0x0800 and l2 + 20 <= len
+ * (l2 = 18 behind a tag, else 14; the version nibble is not tested). The ports sit at l4 = l2 + IHL*4
+ * (IHL 0-4 puts them inside the IPv4 header, as the reference does) and need protocol 6 with
+ * l4 + 19 <= len or protocol 17 with l4 + 8 <= len. No byte past 81 is read.
+ * nfcs_acl_set_rules copies its array (NULL with n > 0: NFCS_EINVAL) and invalidates an earlier commit:
+ * nfcs_acl_eval_host then returns NFCS_EINVAL until the next nfcs_acl_commit. An earlier upload is NOT
+ * invalidated: nfcs_acl_eval_device keeps serving the rules of the last nfcs_acl_upload, exactly as
+ * with nfcs_fib. A caller that needs host and device answers equal uploads after every commit. */
+typedef struct nfcs_acl nfcs_acl;
+NFCS_API int nfcs_acl_create(nfcs_acl** out);
+NFCS_API int nfcs_acl_destroy(nfcs_acl* acl); /* also frees what nfcs_acl_upload allocated */
+NFCS_API int nfcs_acl_set_rules(nfcs_acl* acl, const nfcs_acl_rule* rules, uint32_t n);
+NFCS_API int nfcs_acl_commit(nfcs_acl* acl);
+/* Copies the committed rules to ctx's device (synchronous; replaces an earlier upload, which must no
+ * longer be in use). NFCS_EINVAL before nfcs_acl_commit. The acl must be destroyed before ctx. */
+NFCS_API int nfcs_acl_upload(nfcs_ctx* ctx, nfcs_acl* acl);
+/* The decision for one frame on the CPU, from the same compiled arrays the kernel reads:
+ * *action = NFCS_ACL_PERMIT / DENY / REDIRECT, *rule_index = the deciding rule's index in the list or
+ * NFCS_ACL_NO_MATCH, *redirect_port = the port for NFCS_ACL_REDIRECT, else NFCS_IF_NONE (each may be
+ * NULL). frame may be NULL when len is 0. NFCS_EINVAL before nfcs_acl_commit. */
+NFCS_API int nfcs_acl_eval_host(const nfcs_acl* acl, const uint8_t* frame, uint32_t len, uint32_t* action,
+                                uint32_t* rule_index, uint32_t* redirect_port);
+
+/* Batched AclManager::evaluate over device-resident frames: one kernel, read-only on the frames
+ * (bytes 0..95 of each at most), asynchronous on the stream.
+ *   d_action    n bytes NFCS_ACL_*
+ *   d_rule      optional (NULL) n u32: the index of the deciding rule, or NFCS_ACL_NO_MATCH
+ *   d_redirect  optional (NULL) n u32: the port for NFCS_ACL_REDIRECT, else NFCS_IF_NONE
+ *   d_nh        optional (NULL) n u32, IN/OUT: d_nh[i] = NFCS_NH_NONE for every packet whose action is
+ *               not NFCS_ACL_PERMIT; every other entry is left as it is (a store, not a read-modify-
+ *               write). In stream order nfcs_route_lookup_device -> this -> nfcs_l3_forward_device
+ *               forwards only permitted packets with no host step (the ingress ACL); the same call
+ *               after the forward, on the egress port's rules, serves the egress ACL.
+ * n == 0 returns NFCS_OK without a launch. acl must be uploaded to ctx (else NFCS_EINVAL) and stay
+ * unchanged until the call completes.
+ * ONE rule list per call. Choosing the list per packet (ports bound to different ACLs inside one
+ * burst) is out of scope: the scan is wave-uniform, every lane reading the same rule, and a list per
+ * lane would make it diverge. RX bursts arrive per port; a caller with a mixed burst groups it by
+ * port first. */
+NFCS_API int nfcs_acl_eval_device(nfcs_ctx* ctx, const nfcs_acl* acl, const uint8_t* d_arena,
+                                  uint64_t arena_bytes, const nfcs_desc* d_desc, uint32_t n,
+                                  uint8_t* d_action, uint32_t* d_rule, uint32_t* d_redirect,
+                                  uint32_t* d_nh, void* stream);
 
 /* ---- VLAN push / pop + checksum ---------------------------------------- */
 

@@ -46,6 +46,20 @@ FIB_ROUTE_DTYPE = np.dtype([("network", "<u4"), ("mask", "<u4"), ("next_hop_ip",
 FIB_ARP_DTYPE = np.dtype([("ip", "<u4"), ("mac", "u1", (6,)), ("pad", "u1", (2,))])
 FIB_IF_MAC_DTYPE = np.dtype([("egress_if", "<u4"), ("mac", "u1", (6,)), ("pad", "u1", (2,))])
 
+# nfcs_acl_eval_device / nfcs_acl_eval_host (include/nfcs.h NFCS_ACL_*)
+ACL_PERMIT, ACL_DENY, ACL_REDIRECT, ACL_BAD_DESC = range(4)
+ACL_NO_MATCH = 0xFFFFFFFF
+ACL_MAX_RULES = 512
+ACL_GROUP = 4  # rules per trip of the kernel's scan (csrc/nfcs_acl.h kAclGroup)
+(ACL_F_SRC_MAC, ACL_F_DST_MAC, ACL_F_VLAN_ID, ACL_F_ETHERTYPE, ACL_F_SRC_IP, ACL_F_DST_IP, ACL_F_PROTOCOL,
+ ACL_F_SRC_PORT, ACL_F_DST_PORT) = (1 << k for k in range(9))
+# nfcs_acl_rule: addresses and their masks in HOST byte order (10.1.2.3 = 0x0A010203), unlike the FIB's
+ACL_RULE_DTYPE = np.dtype([("fields", "<u4"), ("rule_id", "<u4"), ("src_mac", "u1", (6,)), ("dst_mac", "u1", (6,)),
+                           ("vlan_id", "<u2"), ("ethertype", "<u2"), ("src_ip", "<u4"), ("dst_ip", "<u4"),
+                           ("src_ip_mask", "<u4"), ("dst_ip_mask", "<u4"), ("src_port", "<u2"), ("dst_port", "<u2"),
+                           ("protocol", "u1"), ("action", "u1"), ("pad", "u1", (2,)), ("redirect_port", "<u4")])
+assert ACL_RULE_DTYPE.itemsize == 52
+
 NEXTHOP_DTYPE = np.dtype([("dst_mac", "u1", (6,)), ("src_mac", "u1", (6,))])
 FLOW_KEY_DTYPE = np.dtype([("hash", "<u4"), ("vlan_id", "<u2"), ("ethertype", "<u2"),
                            ("src_mac", "u1", (6,)), ("dst_mac", "u1", (6,)), ("protocol", "u1"),
@@ -145,6 +159,14 @@ def _declare(L):
         "nfcs_fib_lookup_host": ([_vp, _u32, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32),
                                   ctypes.POINTER(_u32)], ctypes.c_int),
         "nfcs_route_lookup_device": ([_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp], ctypes.c_int),
+        "nfcs_acl_create": ([ctypes.POINTER(_vp)], ctypes.c_int),
+        "nfcs_acl_destroy": ([_vp], ctypes.c_int),
+        "nfcs_acl_set_rules": ([_vp, _vp, _u32], ctypes.c_int),
+        "nfcs_acl_commit": ([_vp], ctypes.c_int),
+        "nfcs_acl_upload": ([_vp, _vp], ctypes.c_int),
+        "nfcs_acl_eval_host": ([_vp, _vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32),
+                                ctypes.POINTER(_u32)], ctypes.c_int),
+        "nfcs_acl_eval_device": ([_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         # a measurement build of an earlier round (NFCS_LIB, A/B runs) may lack a later entry point;
@@ -269,6 +291,60 @@ class Fib:
     def close(self):
         if getattr(self, "ptr", None):
             lib().nfcs_fib_destroy(self.ptr)
+            self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Acl:
+    """One ACL rule list behind Engine.acl_eval_device (nfcs_acl): ACL_RULE_DTYPE records scanned in the
+    order given, the first match decides (pass AclManager::get_all_rules(name) as it is), no match
+    permits. Addresses and their masks are u32 in HOST byte order (10.1.2.3 = 0x0A010203), as AclRule
+    holds them, unlike the Fib's network-order ones."""
+
+    def __init__(self):
+        p = _vp()
+        _check(lib().nfcs_acl_create(ctypes.byref(p)), "nfcs_acl_create")
+        self.ptr = p.value
+
+    def set_rules(self, rules):
+        """ACL_RULE_DTYPE records, in scan order; at most ACL_MAX_RULES."""
+        rules = np.ascontiguousarray(rules, dtype=ACL_RULE_DTYPE)
+        _check(lib().nfcs_acl_set_rules(self.ptr, rules.ctypes.data if len(rules) else None, len(rules)),
+               "nfcs_acl_set_rules")
+        return self
+
+    def commit(self):
+        _check(lib().nfcs_acl_commit(self.ptr), "nfcs_acl_commit")
+        return self
+
+    def upload(self, engine: "Engine"):
+        """Copy the committed rules to the engine's device; close the Acl before the engine."""
+        _check(lib().nfcs_acl_upload(engine.ctx, self.ptr), "nfcs_acl_upload")
+        return self
+
+    def eval_host(self, frame: bytes) -> tuple[int, int, int]:
+        """(action, index of the deciding rule or ACL_NO_MATCH, redirect port or IF_NONE) for one frame,
+        on the CPU, from the arrays the kernel reads (nfcs_acl_eval_host)."""
+        a, r, p = _u32(), _u32(), _u32()
+        frame = bytes(frame)
+        _check(lib().nfcs_acl_eval_host(self.ptr, frame if frame else None, len(frame), ctypes.byref(a),
+                                        ctypes.byref(r), ctypes.byref(p)), "nfcs_acl_eval_host")
+        return int(a.value), int(r.value), int(p.value)
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            lib().nfcs_acl_destroy(self.ptr)
             self.ptr = None
 
     def __enter__(self):
@@ -454,6 +530,16 @@ class Engine:
         ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
         _check(lib().nfcs_route_lookup_device(self.ctx, fib.ptr, ptr(arena), arena_bytes, ptr(desc), n, ptr(nh),
                                               ptr(egress_if), ptr(verdict), stream), "nfcs_route_lookup_device")
+
+    def acl_eval_device(self, acl: Acl, arena, arena_bytes: int, desc, n: int, action, rule=None, redirect=None,
+                        nh=None, stream=None):
+        """AclManager::evaluate per frame on device frames, read-only: action = n bytes ACL_*; rule (n u32:
+        the deciding rule's index or ACL_NO_MATCH), redirect (n u32: the REDIRECT port or IF_NONE) and nh
+        (n u32, in/out: NH_NONE stored where the action is not ACL_PERMIT, the rest untouched) optional.
+        Between route_lookup_device and l3_forward_device with their nh it is the ingress ACL."""
+        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
+        _check(lib().nfcs_acl_eval_device(self.ctx, acl.ptr, ptr(arena), arena_bytes, ptr(desc), n, ptr(action),
+                                          ptr(rule), ptr(redirect), ptr(nh), stream), "nfcs_acl_eval_device")
 
     def vlan_device(self, arena, arena_bytes: int, desc, n: int, ops=None, op_all: int = 0,
                     caps=None, cap_all: int = 0, status=None, stream=None):

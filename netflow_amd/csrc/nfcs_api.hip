@@ -1126,6 +1126,118 @@ NFCS_API int nfcs_route_lookup_device(nfcs_ctx* c, const nfcs_fib* f, const uint
     return NFCS_OK;
 }
 
+// ---- ACL (nfcs_acl.h: compile, host decision) and its evaluation kernel --------------------------
+}  // extern "C"
+
+struct nfcs_acl {
+    std::vector<nfcs_acl_rule> in;
+    nfcs::AclTables t;
+    bool committed = false;
+    // nfcs_acl_upload: one device allocation holding both arrays, on `device`
+    int device = -1;
+    uint8_t* d_blob = nullptr;
+    nfcs::AclDev dev;
+    bool uploaded = false;
+};
+
+namespace {
+void acl_drop_upload(nfcs_acl* a) {
+    if (a->d_blob) {
+        DeviceGuard dg_(a->device);
+        if (dg_.err == hipSuccess) (void)hipFree(a->d_blob);
+    }
+    a->d_blob = nullptr;
+    a->dev = nfcs::AclDev{};
+    a->uploaded = false;
+}
+}  // namespace
+
+extern "C" {
+
+NFCS_API int nfcs_acl_create(nfcs_acl** out) {
+    if (!out) return NFCS_EINVAL;
+    *out = new (std::nothrow) nfcs_acl();
+    return *out ? NFCS_OK : NFCS_ENOMEM;
+}
+
+NFCS_API int nfcs_acl_destroy(nfcs_acl* a) {
+    if (!a) return NFCS_EINVAL;
+    acl_drop_upload(a);
+    delete a;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_acl_set_rules(nfcs_acl* a, const nfcs_acl_rule* rules, uint32_t n) {
+    if (!a || (n > 0 && !rules) || n > NFCS_ACL_MAX_RULES) return NFCS_EINVAL;
+    for (uint32_t i = 0; i < n; ++i)
+        if ((rules[i].fields & ~NFCS_ACL_F_ALL) || rules[i].action > NFCS_ACL_REDIRECT) return NFCS_EINVAL;
+    try {
+        a->in.assign(rules, rules + n);
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+    a->committed = false;  // the device copy, if any, stays as it is until the next upload
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_acl_commit(nfcs_acl* a) {
+    if (!a) return NFCS_EINVAL;
+    try {
+        nfcs::acl_compile(a->in, a->t);
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+    a->committed = true;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_acl_upload(nfcs_ctx* c, nfcs_acl* a) {
+    if (!c || !a || !a->committed) return NFCS_EINVAL;
+    acl_drop_upload(a);
+    DeviceGuard dg_(c->di.device);
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    const nfcs::AclTables& t = a->t;
+    // one blob: the records (64 bytes each), then the actions
+    const size_t o_act = t.rec.size() * sizeof(nfcs::AclRec), total = o_act + t.act.size() * sizeof(nfcs::AclAct);
+    std::vector<uint8_t> blob(total + 16u, 0);
+    if (!t.rec.empty()) memcpy(blob.data(), t.rec.data(), o_act);
+    if (!t.act.empty()) memcpy(blob.data() + o_act, t.act.data(), total - o_act);
+    NFCS_HIP(hipMalloc(&a->d_blob, blob.size()));
+    a->device = c->di.device;
+    const hipError_t e = hipMemcpy(a->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        acl_drop_upload(a);
+        return hip_fail(e);
+    }
+    a->dev.rec = (const uint4*)a->d_blob;
+    a->dev.act = (const uint2*)(a->d_blob + o_act);
+    a->dev.rules = t.rules;
+    a->dev.rules_padded = (uint32_t)t.rec.size();
+    a->uploaded = true;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_acl_eval_host(const nfcs_acl* a, const uint8_t* frame, uint32_t len, uint32_t* action,
+                                uint32_t* rule_index, uint32_t* redirect_port) {
+    if (!a || !a->committed || (len > 0 && !frame)) return NFCS_EINVAL;
+    nfcs::acl_decide(a->t, frame, len, action, rule_index, redirect_port);
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_acl_eval_device(nfcs_ctx* c, const nfcs_acl* a, const uint8_t* d_arena, uint64_t arena_bytes,
+                                  const nfcs_desc* d_desc, uint32_t n, uint8_t* d_action, uint32_t* d_rule,
+                                  uint32_t* d_redirect, uint32_t* d_nh, void* stream) {
+    if (!c || !a || !a->uploaded || a->device != c->di.device) return NFCS_EINVAL;
+    DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    if (n == 0) return NFCS_OK;
+    if (!d_arena || !d_desc || !d_action || ((uintptr_t)d_arena & 15u)) return NFCS_EINVAL;
+    if (((uintptr_t)d_rule & 3u) || ((uintptr_t)d_redirect & 3u) || ((uintptr_t)d_nh & 3u)) return NFCS_EINVAL;
+    NFCS_HIP(nfcs::launch_acl_eval(c->di, a->dev, d_arena, arena_bytes, d_desc, n, d_action, d_rule, d_redirect, d_nh,
+                                   pick(c, stream)));
+    return NFCS_OK;
+}
+
 NFCS_API int nfcs_update_host(nfcs_ctx* c, uint8_t* h_arena, uint64_t arena_bytes,
                               const nfcs_desc* h_desc, uint32_t n, uint8_t* h_status,
                               uint32_t flags) {

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "nfcs.h"
+#include "nfcs_acl.h"
 #include "nfcs_fib.h"
 
 namespace nfcs {
@@ -199,6 +200,17 @@ struct FibDev {
 hipError_t launch_route_lookup(const DevInfo& di, const FibDev& fib, const uint8_t* arena, uint64_t arena_bytes,
                                const nfcs_desc* desc, uint32_t n, uint32_t* nh, uint32_t* egress_if,
                                uint8_t* verdict, hipStream_t stream);
+
+// The committed ACL in device memory (nfcs_acl_upload; the arrays of AclTables, nfcs_acl.h).
+struct AclDev {
+    const uint4* rec = nullptr;  // rules_padded 64-byte records {value[8], mask[8]}, 16-byte aligned
+    const uint2* act = nullptr;  // rules {action, redirect port}
+    uint32_t rules = 0, rules_padded = 0;
+};
+
+hipError_t launch_acl_eval(const DevInfo& di, const AclDev& acl, const uint8_t* arena, uint64_t arena_bytes,
+                           const nfcs_desc* desc, uint32_t n, uint8_t* action, uint32_t* rule, uint32_t* redirect,
+                           uint32_t* nh, hipStream_t stream);
 
 hipError_t launch_gen_config(const DevInfo& di, int config, uint64_t seed, uint64_t first,
                              uint32_t n, uint8_t* arena, uint64_t arena_bytes,

@@ -2221,6 +2221,185 @@ hipError_t launch_route_lookup(const DevInfo& di, const FibDev& fib, const uint8
     return hipGetLastError();
 }
 
+// ---- ACL evaluation in front of the lookup and the forward --------------------
+// AclManager::evaluate (acl_manager.cpp:161-278) per packet, in flow_keys_lanes_kernel's shape: a wave
+// takes 64 packets, loads header bytes 0..47 in 8-lane rows, one line per packet, lane l reads packet l
+// from LDS (96 bytes per packet; headers whose ports lie past byte 47 — IPv4 options — load chunks 3..5
+// afterwards, lane by lane) and folds every field check_match can read into a key of eight dwords
+// (nfcs_acl.h acl_key). The compiled rules {value[8], mask[8]} are staged once per workgroup in LDS
+// behind the header rows and scanned in the given order by a wave-uniform loop: every lane reads the
+// same rule (LDS broadcasts), kAclGroup rules per trip folded last to first so the first in order wins,
+// one ballot per trip, and the wave leaves the loop once each of its live lanes has its match. A trip
+// reads the rules' address / port / protocol halves first and their MAC / VLAN / EtherType halves only
+// when one of its rules tests those (half the LDS traffic for a list of address and port rules).
+constexpr uint32_t kAclRowsBytes = kWavesPerBlock * 64u * kFkRow;
+static_assert(kAclRowsBytes + NFCS_ACL_MAX_RULES * sizeof(AclRec) < 64u * 1024u,
+              "header rows + rules stay under 64 KiB of dynamic LDS (no opt-in needed)");
+
+__global__ __launch_bounds__(kBlock) void acl_eval_kernel(const nfcs_desc* __restrict__ desc, uint32_t n,
+                                                          uint32_t nblocks, const uint8_t* __restrict__ arena,
+                                                          uint64_t arena_bytes, const AclDev acl,
+                                                          uint8_t* __restrict__ action_out,
+                                                          uint32_t* __restrict__ rule_out,
+                                                          uint32_t* __restrict__ redirect_out,
+                                                          uint32_t* __restrict__ nh_out) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t acl_lds[];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t p0 = ((uint64_t)xcd_block_n(nblocks) * kWavesPerBlock + rfl(wave)) * 64u;
+    uint8_t* rows = acl_lds + wave * 64u * kFkRow;
+    // lane l: descriptor of packet p0 + l (one coalesced load); dead packets read as length 0
+    const uint64_t p = p0 + lane;
+    uint2 dl = make_uint2(0u, 0u);
+    if (p < n) dl = ((const uint2*)desc)[p];
+    const uint64_t off = (uint64_t)dl.x * 16u;
+    const bool live = p < n && off + (((uint64_t)dl.y + 15u) & ~15ull) <= arena_bytes;
+    const uint32_t len = live ? dl.y : 0u;
+    // header chunks 0..2 in 8-lane rows (instruction k, row r -> packet 8k + r, lane rl -> chunk rl),
+    // non-temporal: the frames are read once
+    const uint32_t rl = lane & 7u, r = lane >> 3;
+    const uint4* zl = g_zero_line;
+    uint4 c[8];
+    if (p0 < n) {
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) {
+            const uint32_t q = 8u * k + r;
+            const uint32_t qo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)dl.x);
+            const uint32_t ql = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)len);
+            const uint4* src = (const uint4*)(arena + (uint64_t)qo * 16u);
+            c[k] = ld16<1>((rl < 3u && rl * 16u < ql) ? src + rl : zl);
+        }
+    }
+    // the compiled rules, four 16-byte pieces each, once per workgroup (every wave of the workgroup
+    // takes part, also one past n: it leaves after the barrier)
+    uint4* rec4 = (uint4*)(acl_lds + kAclRowsBytes);
+    const uint32_t n4 = acl.rules_padded * 4u;
+    for (uint32_t i0 = 0; i0 < n4; i0 += 4u * kBlock) {  // 4 loads in flight per lane (index clamped, not branched)
+        uint4 t[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t i = i0 + j * kBlock + threadIdx.x;
+            t[j] = acl.rec[i < n4 ? i : n4 - 1u];
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t i = i0 + j * kBlock + threadIdx.x;
+            if (i < n4) rec4[i] = t[j];
+        }
+    }
+    __syncthreads();
+    if (p0 >= n) return;
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k)
+        if (rl < 3u) *(uint4*)(rows + (8u * k + r) * kFkRow + 16u * rl) = c[k];
+    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes are done
+    __builtin_amdgcn_wave_barrier();
+    // lane l builds the key of packet l (nfcs_acl.h acl_key, the same bounds)
+    uint8_t* b = rows + lane * kFkRow;
+    const uint32_t e12 = lds_be16(b, 12);
+    const bool eth = len >= 14, tagged = e12 == 0x8100u;
+    const uint32_t sh = tagged ? 4u : 0u;  // l2 = 18 behind a tag
+    const bool known = eth && (!tagged || len >= 18);
+    const uint32_t et = !known ? 0u : tagged ? lds_be16(b, 16) : e12;
+    const bool v4 = known && et == 0x0800u && 34u + sh <= len;  // ipv4() present
+    const uint32_t l4 = 14u + sh + (lds_u8(b, 14u + sh) & 15u) * 4u;
+    {  // the ports end at l4 + 4: past byte 47 only with IPv4 options (IHL >= 8; 7 behind a tag)
+        const bool more = v4 && l4 + 4u > 48u && len > 48u;
+        if (__builtin_amdgcn_ballot_w64(more) != 0) {
+            if (more) {
+                const uint4* src = (const uint4*)(arena + off);
+#pragma unroll
+                for (uint32_t j = 3; j < 6; ++j) *(uint4*)(b + 16u * j) = ld16<0>(16u * j < len ? src + j : zl);
+            }
+            __builtin_amdgcn_s_waitcnt(0xc07f);
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    uint32_t key[8];
+    key[kAkMac0] = eth ? *(const uint32_t*)b : 0u;
+    key[kAkMac1] = eth ? *(const uint32_t*)(b + 4) : 0u;
+    key[kAkMac2] = eth ? *(const uint32_t*)(b + 8) : 0u;
+    const bool has_vid = eth && tagged && len >= 18;
+    key[kAkL2] = (has_vid ? lds_be16(b, 14) & 0x0FFFu : 0u) | (et << 16);
+    uint32_t meta = (eth ? kApEth : 0u) | (has_vid ? kApVlan : 0u) | (known ? kApEtype : 0u);
+    uint32_t sip = 0, dip = 0, ports = 0;
+    if (v4) {
+        sip = __builtin_bswap32(lds_le32(b, 26u + sh));  // ntohl: AclRule holds host order
+        dip = __builtin_bswap32(lds_le32(b, 30u + sh));
+        const uint32_t proto = lds_u8(b, 23u + sh);
+        meta |= kApIpv4 | proto;
+        // tcp() needs l4 + 19 <= len (19-byte TcpHeader), udp() l4 + 8 (packet.hpp:473-541)
+        if ((proto == 6 && l4 + 19u <= len) || (proto == 17 && l4 + 8u <= len)) {
+            meta |= kApPorts;
+            ports = lds_be16(b, l4) | (lds_be16(b, l4 + 2u) << 16);
+        }
+    }
+    key[kAkSrcIp] = sip;
+    key[kAkDstIp] = dip;
+    key[kAkPorts] = ports;
+    key[kAkMeta] = meta;
+    // the scan: rule i + j matches when ((key ^ value) & mask) == 0 over the eight dwords
+    const uint4* rec = (const uint4*)(acl_lds + kAclRowsBytes);
+    uint32_t match = NFCS_ACL_NO_MATCH;
+    for (uint32_t i = 0; i < acl.rules_padded; i += kAclGroup) {
+        if (__builtin_amdgcn_ballot_w64(live && match == NFCS_ACL_NO_MATCH) == 0) break;
+        // dwords 4..7 (addresses, ports, protocol and presence bits) of the trip's rules first; dwords 0..3
+        // (MACs, VLAN id, EtherType) only when one of these rules tests them, which its mask says in a
+        // bit no key has (kApNeedL2). The rules are the same for every lane, so the branch is uniform.
+        uint32_t d[kAclGroup], l2 = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < kAclGroup; ++j) {
+            const uint4* e = rec + (i + j) * 4u;
+            const uint4 v1 = e[1], m1 = e[3];
+            d[j] = (key[4] ^ v1.x) & m1.x;
+            d[j] |= (key[5] ^ v1.y) & m1.y;
+            d[j] |= (key[6] ^ v1.z) & m1.z;
+            d[j] |= (key[7] ^ v1.w) & m1.w;
+            l2 |= m1.w;
+        }
+        if (rfl(l2) & kApNeedL2) {
+#pragma unroll
+            for (uint32_t j = 0; j < kAclGroup; ++j) {
+                const uint4* e = rec + (i + j) * 4u;
+                const uint4 v0 = e[0], m0 = e[2];
+                d[j] |= (key[0] ^ v0.x) & m0.x;
+                d[j] |= (key[1] ^ v0.y) & m0.y;
+                d[j] |= (key[2] ^ v0.z) & m0.z;
+                d[j] |= (key[3] ^ v0.w) & m0.w;
+            }
+        }
+        uint32_t m = NFCS_ACL_NO_MATCH;
+#pragma unroll
+        for (uint32_t j = kAclGroup; j-- > 0;) m = d[j] == 0 ? i + j : m;  // descending: the first rule in order wins
+        match = match == NFCS_ACL_NO_MATCH ? m : match;
+    }
+    uint32_t action = live ? NFCS_ACL_PERMIT : NFCS_ACL_BAD_DESC, redirect = NFCS_IF_NONE;
+    if (live && match != NFCS_ACL_NO_MATCH) {  // match < acl.rules: the padding rules match nothing
+        const uint2 a = acl.act[match];
+        action = a.x;
+        redirect = a.y;
+    }
+    if (!live) match = NFCS_ACL_NO_MATCH;
+    if (p < n) {  // one packet per lane: each store instruction writes consecutive elements
+        action_out[p] = (uint8_t)action;
+        if (rule_out) rule_out[p] = match;
+        if (redirect_out) redirect_out[p] = redirect;
+        if (nh_out && action != NFCS_ACL_PERMIT) nh_out[p] = NFCS_NH_NONE;  // a predicated store, no read
+    }
+}
+
+hipError_t launch_acl_eval(const DevInfo& di, const AclDev& acl, const uint8_t* arena, uint64_t arena_bytes,
+                           const nfcs_desc* desc, uint32_t n, uint8_t* action, uint32_t* rule, uint32_t* redirect,
+                           uint32_t* nh, hipStream_t stream) {
+    (void)di;
+    if (n == 0) return hipSuccess;
+    // 64 packets per wave, one lane each, XCD-aware order; LDS: the header rows, then the rules
+    const uint32_t g = (n + 255u) / 256u;
+    const unsigned lds = kAclRowsBytes + acl.rules_padded * (unsigned)sizeof(AclRec);
+    hipLaunchKernelGGL(acl_eval_kernel, dim3(g), dim3(kBlock), lds, stream, desc, n, g, arena, arena_bytes, acl, action,
+                       rule, redirect, nh);
+    return hipGetLastError();
+}
+
 // ---- synthetic config generator (same spec as oracle/nfcs_oracle.c) -----------
 constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
 __host__ __device__ inline uint64_t mix64(uint64_t z) {
