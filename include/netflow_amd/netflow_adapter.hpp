@@ -22,6 +22,9 @@
 //   AclManager::evaluate                      netflow_amd::acl_eval_batch(pkts, acl, action[, rule_index,
 //        acl_manager.cpp:161-278              redirect_port, next_hop]) with acl = netflow_amd::make_acl(
 //                                             acl_manager.get_all_rules(name)): masks next_hop for l3_forward_batch
+//   fdb.lookup_port, the same-port / link /   netflow_amd::l2_lookup_batch(pkts, fdb, ingress_port, egress_port[,
+//   STP / should_forward checks, flood        verdict, vlan, learn, rt_verdict]) with fdb = netflow_amd::make_fdb(
+//        switch.hpp:305-326                   fdb, vlan_manager, link_up, stp_forwarding, num_ports)
 //
 // Every entry returns 0 or a negative NFCS_E* code and never throws (the reference's calls are
 // void / bool and never throw); per-packet outcomes are the NFCS_ST_* status bytes. The bytes
@@ -45,6 +48,8 @@
 namespace netflow {
 class RoutingManager;  // <netflow++/routing_manager.hpp>, for make_fib below
 struct AclRule;        // <netflow++/acl_manager.hpp>, for make_acl below
+class ForwardingDatabase;  // <netflow++/forwarding_database.hpp>, for make_fdb below
+class VlanManager;         // <netflow++/vlan_manager.hpp>, for make_fdb below
 }
 
 namespace netflow_amd {
@@ -136,6 +141,36 @@ inline int acl_eval_batch(const std::vector<netflow::Packet*>& pkts, const nfcs_
 template <class AclRuleT = netflow::AclRule>
 inline int make_acl(const std::vector<AclRuleT>& rules, nfcs_acl** out) {
     return make_acl_from(rules, out);
+}
+
+inline int l2_lookup_batch(netflow::Packet* const* pkts, size_t n, const nfcs_fdb* fdb, uint32_t ingress_port,
+                           uint32_t* egress_port, uint8_t* verdict = nullptr, uint16_t* vlan = nullptr,
+                           uint8_t* learn = nullptr, const uint8_t* rt_verdict = nullptr) {
+    return detail::on_default_engine([&](ChecksumEngine& e) {
+        return e.l2_lookup_batch(pkts, n, fdb, ingress_port, egress_port, verdict, vlan, learn, rt_verdict);
+    });
+}
+inline int l2_lookup_batch(const std::vector<netflow::Packet*>& pkts, const nfcs_fdb* fdb, uint32_t ingress_port,
+                           uint32_t* egress_port, uint8_t* verdict = nullptr, uint16_t* vlan = nullptr,
+                           uint8_t* learn = nullptr, const uint8_t* rt_verdict = nullptr) {
+    return l2_lookup_batch(pkts.data(), pkts.size(), fdb, ingress_port, egress_port, verdict, vlan, learn, rt_verdict);
+}
+
+// A committed forwarding database (nfcs_fdb) from the switch's own L2 state: ForwardingDatabase::
+// get_all_entries() as it is, and for the ports 0 .. num_ports - 1 VlanManager::get_port_config plus the
+// two predicates the L2 block asks per port — link_up(port) for InterfaceManager::is_port_link_up and
+// stp_forwarding(port) for StpManager::get_port_stp_state(port) == PortState::FORWARDING, as callables,
+// so that this header needs neither manager. Returns NFCS_OK and the database in *out (nfcs_fdb_destroy
+// it; upload it with ChecksumEngine::upload_fdb before l2_lookup_batch), or a negative NFCS_E* code. A
+// template, so that <netflow++/forwarding_database.hpp> and <netflow++/vlan_manager.hpp> are needed only
+// where make_fdb is used: the caller includes them and links forwarding_database.cpp and
+// vlan_manager.cpp, as any user of those classes does. The work is netflow_amd::make_fdb_from
+// (packet.hpp), which any types with the same member names can use.
+template <class ForwardingDatabaseT = netflow::ForwardingDatabase, class VlanManagerT = netflow::VlanManager,
+          class LinkUp, class StpForwarding>
+inline int make_fdb(const ForwardingDatabaseT& fdb, const VlanManagerT& vlans, LinkUp&& link_up,
+                    StpForwarding&& stp_forwarding, uint32_t num_ports, nfcs_fdb** out) {
+    return make_fdb_from(fdb, vlans, link_up, stp_forwarding, num_ports, out);
 }
 
 // On an engine of the caller's (another device; one engine per GPU, one host thread each).

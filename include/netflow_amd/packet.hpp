@@ -22,7 +22,10 @@
 // (nfcs_flow_keys_device: 64-byte FlowKey records in host order + hash_flow values); and
 // AclManager::evaluate (acl_manager.cpp:161-278) for a burst, from a rule list built by make_acl_from
 //   netflow_amd::acl_eval_batch(Packet* const*, size_t, const nfcs_acl*, uint8_t* action, ...)
-// (nfcs_acl_eval_device: the first matching rule in the given order; masks a next-hop vector).
+// (nfcs_acl_eval_device: the first matching rule in the given order; masks a next-hop vector); and
+// the switch's L2 data plane (switch.hpp:305-326) for a burst, from a database built by make_fdb_from
+//   netflow_amd::l2_lookup_batch(Packet* const*, size_t, const nfcs_fdb*, ingress_port, egress_port, ...)
+// (nfcs_l2_lookup_device: FDB lookup, same-port / link / STP / VLAN checks, flood, learn classes).
 //
 // The batch entry points are templates over the packet type: they take this header's Packet or
 // the reference's own netflow::Packet (include/netflow_amd/netflow_adapter.hpp), whose buffers
@@ -240,6 +243,25 @@ public:
     int upload_acl(nfcs_acl* acl) {
         std::lock_guard<std::mutex> lock(mu_);
         return nfcs_acl_upload(ctx_, acl);
+    }
+
+    // The switch's L2 data plane (switch.hpp:305-326) for a batch received on ingress_port, from a
+    // committed forwarding database (nfcs_fdb_*; upload_fdb first): egress_port[i] = the port for
+    // NFCS_L2_FORWARD or NFCS_IF_NONE, verdict[i] (optional) = NFCS_L2_*, vlan[i] (optional) = the VLAN
+    // used for the lookup, learn[i] (optional) = NFCS_L2_LEARN_*, what learn_mac(src_mac, ingress_port,
+    // vlan) would do (the table is not changed). rt_verdict (optional, n bytes from route_lookup_batch
+    // on the same packets): only NFCS_RT_NOT_IPV4 packets are decided, the others read NFCS_L2_SKIP.
+    // Reads the first 32 bytes of each packet at most (the decision tests lengths against 14 and 18
+    // only); the packets are not changed.
+    template <class Pkt>
+    int l2_lookup_batch(Pkt* const* pkts, size_t n, const nfcs_fdb* fdb, uint32_t ingress_port,
+                        uint32_t* egress_port, uint8_t* verdict = nullptr, uint16_t* vlan = nullptr,
+                        uint8_t* learn = nullptr, const uint8_t* rt_verdict = nullptr);
+    // nfcs_fdb_upload to this engine's device, serialised with its other calls. The fdb must be
+    // destroyed before the engine.
+    int upload_fdb(nfcs_fdb* fdb) {
+        std::lock_guard<std::mutex> lock(mu_);
+        return nfcs_fdb_upload(ctx_, fdb);
     }
 
     nfcs_ctx* ctx() const { return ctx_; }
@@ -626,6 +648,40 @@ int ChecksumEngine::acl_eval_batch(Pkt* const* pkts, size_t n, const nfcs_acl* a
     return NFCS_OK;
 }
 
+template <class Pkt>
+int ChecksumEngine::l2_lookup_batch(Pkt* const* pkts, size_t n, const nfcs_fdb* fdb, uint32_t ingress_port,
+                                    uint32_t* egress_port, uint8_t* verdict, uint16_t* vlan, uint8_t* learn,
+                                    const uint8_t* rt_verdict) {
+    if (n == 0) return NFCS_OK;
+    if (!pkts || !fdb || !egress_port || n > 0xFFFFFFFFu) return NFCS_EINVAL;
+    std::lock_guard<std::mutex> lock(mu_);
+    // gather clamps each length to 32: the decision tests lengths against 14 and 18 only
+    int rc = reserve(n * 32 + 16, n);
+    if (rc) return rc;
+    const size_t off = gather(pkts, n, 32);
+    DevTmp dport(ctx_, n * sizeof(uint32_t), rc);
+    DevTmp dvlan(ctx_, n * sizeof(uint16_t), rc);
+    DevTmp dlearn(ctx_, n, rc);
+    DevTmp drt(ctx_, n, rc);
+    if (rc) return rc;
+    const uint32_t m = static_cast<uint32_t>(n);
+    if ((rc = nfcs_memcpy_h2d(ctx_, d_arena_, h_arena_, off ? off : 16))) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, d_desc_, h_desc_, n * sizeof(nfcs_desc)))) return rc;
+    if (rt_verdict && (rc = nfcs_memcpy_h2d(ctx_, drt.p, rt_verdict, n))) return rc;
+    if ((rc = nfcs_l2_lookup_device(ctx_, fdb, ingress_port, static_cast<uint8_t*>(d_arena_), off ? off : 16,
+                                    static_cast<nfcs_desc*>(d_desc_), m,
+                                    rt_verdict ? static_cast<uint8_t*>(drt.p) : nullptr,
+                                    static_cast<uint32_t*>(dport.p), static_cast<uint8_t*>(d_status_),
+                                    static_cast<uint16_t*>(dvlan.p),
+                                    learn ? static_cast<uint8_t*>(dlearn.p) : nullptr, nullptr)))
+        return rc;
+    if ((rc = nfcs_memcpy_d2h(ctx_, egress_port, dport.p, n * sizeof(uint32_t)))) return rc;
+    if (verdict && (rc = nfcs_memcpy_d2h(ctx_, verdict, d_status_, n))) return rc;
+    if (vlan && (rc = nfcs_memcpy_d2h(ctx_, vlan, dvlan.p, n * sizeof(uint16_t)))) return rc;
+    if (learn && (rc = nfcs_memcpy_d2h(ctx_, learn, dlearn.p, n))) return rc;
+    return NFCS_OK;
+}
+
 // Same interface as netflow::BufferPool (buffer_pool.hpp:57-123: allocate_buffer(payload,
 // headroom), free_buffer(buffer) with the PacketBuffer reference count), except that every
 // buffer up to slot_bytes is a slot of ONE pinned arena (nfcs_host_alloc). update_checksums_batch
@@ -916,6 +972,60 @@ inline int acl_eval_batch(Packet* const* pkts, size_t n, const nfcs_acl* acl, ui
                           uint32_t* next_hop = nullptr) {
     return detail::on_default_engine(
         [&](ChecksumEngine& e) { return e.acl_eval_batch(pkts, n, acl, action, rule_index, redirect_port, next_hop); });
+}
+// A committed nfcs_fdb from the switch's L2 state, by member name: fdb.get_all_entries() yields entries
+// with mac (a MAC type with `bytes[6]`), vlan_id, port and is_static (ForwardingDatabase's FdbEntry),
+// passed on as they are; vlans.get_port_config(port) yields an optional (operator bool, operator->) of a
+// config with type (an enum or integer with ACCESS 0, TRUNK 1, HYBRID 2), native_vlan and allowed_vlans
+// (any range of VLAN ids: VlanManager::PortConfig); link_up(port) and stp_forwarding(port) are
+// InterfaceManager::is_port_link_up and get_port_stp_state(port) == PortState::FORWARDING as callables.
+// Ports 0 .. num_ports - 1 are set (num_ports at most NFCS_L2_MAX_PORTS). *out: the database
+// (nfcs_fdb_destroy it; upload it with ChecksumEngine::upload_fdb before l2_lookup_batch), or nullptr
+// on error.
+template <class FdbT, class VlanT, class LinkUp, class StpForwarding>
+inline int make_fdb_from(const FdbT& fdb, const VlanT& vlans, LinkUp&& link_up, StpForwarding&& stp_forwarding,
+                         uint32_t num_ports, nfcs_fdb** out) {
+    if (!out) return NFCS_EINVAL;
+    *out = nullptr;
+    std::vector<nfcs_fdb_entry> recs;
+    for (const auto& e : fdb.get_all_entries()) {
+        nfcs_fdb_entry r{};
+        std::memcpy(r.mac, e.mac.bytes, 6);
+        r.vlan_id = e.vlan_id;
+        r.port = e.port;
+        r.is_static = e.is_static ? 1 : 0;
+        recs.push_back(r);
+    }
+    nfcs_fdb* f = nullptr;
+    int rc = nfcs_fdb_create(&f);
+    if (!rc) rc = nfcs_fdb_set_entries(f, recs.data(), static_cast<uint32_t>(recs.size()));
+    for (uint32_t p = 0; !rc && p < num_ports; ++p) {
+        nfcs_l2_port port{};
+        port.port_id = p;
+        port.link_up = link_up(p) ? 1 : 0;
+        port.stp_forwarding = stp_forwarding(p) ? 1 : 0;
+        std::vector<uint16_t> allowed;
+        const auto cfg = vlans.get_port_config(p);
+        if (cfg) {
+            port.has_vlan_config = 1;
+            port.type = static_cast<uint8_t>(static_cast<int>(cfg->type));
+            port.native_vlan = cfg->native_vlan;
+            for (const auto v : cfg->allowed_vlans) allowed.push_back(static_cast<uint16_t>(v));
+        }
+        rc = nfcs_fdb_set_port(f, &port, allowed.data(), static_cast<uint32_t>(allowed.size()));
+    }
+    if (!rc) rc = nfcs_fdb_commit(f);
+    if (rc && f) nfcs_fdb_destroy(f);
+    else *out = f;
+    return rc;
+}
+
+inline int l2_lookup_batch(Packet* const* pkts, size_t n, const nfcs_fdb* fdb, uint32_t ingress_port,
+                           uint32_t* egress_port, uint8_t* verdict = nullptr, uint16_t* vlan = nullptr,
+                           uint8_t* learn = nullptr, const uint8_t* rt_verdict = nullptr) {
+    return detail::on_default_engine([&](ChecksumEngine& e) {
+        return e.l2_lookup_batch(pkts, n, fdb, ingress_port, egress_port, verdict, vlan, learn, rt_verdict);
+    });
 }
 inline int flow_keys_batch(Packet* const* pkts, size_t n, nfcs_flow_key* keys,
                            uint32_t* hashes = nullptr) {

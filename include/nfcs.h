@@ -475,6 +475,147 @@ NFCS_API int nfcs_acl_eval_device(nfcs_ctx* ctx, const nfcs_acl* acl, const uint
                                   uint8_t* d_action, uint32_t* d_rule, uint32_t* d_redirect,
                                   uint32_t* d_nh, void* stream);
 
+/* ---- L2 forwarding: FDB lookup, port / VLAN checks, learning --------------------------------- */
+
+/* The L2 data plane of Switch::process_received_packet (switch.hpp:305-326) for a batch of
+ * device-resident frames: the VLAN used for the lookup, ForwardingDatabase::lookup_port(dst_mac, vlan),
+ * the same-port, link, STP and VlanManager::should_forward checks, flood on a miss, and what
+ * learn_mac(src_mac, ingress_port, vlan) would do. Every frame the route lookup marks
+ * NFCS_RT_NOT_IPV4 ends here. The symbols of this section were added without changing
+ * NFCS_ABI_VERSION (it stays 2): detect them by symbol lookup (dlsym "nfcs_fdb_create").
+ * OUT OF SCOPE: packet replication for floods (nfcs_fdb_flood_ports_host names the ports; the copies
+ * are the caller's); punting ARP, LLDP and BPDU frames (the reference's lines for LLDP and BPDU are
+ * placeholders; the caller classifies with nfcs_flow_keys_device's EtherType); LACP resolution (elided
+ * in the reference); aging; any write to the table from the device. */
+
+/* The decision per packet (d_verdict). */
+enum {
+    NFCS_L2_FORWARD = 0,        /* the entry's port passed every check: d_egress_port[i] is that port    */
+    NFCS_L2_BAD_DESC = 1,       /* the descriptor reaches outside the arena (the frame is not read), or
+                                   d_rt_verdict[i] is NFCS_RT_BAD_DESC                                   */
+    NFCS_L2_SKIP = 2,           /* d_rt_verdict[i] is neither NFCS_RT_NOT_IPV4 nor NFCS_RT_BAD_DESC: the
+                                   L3 block took the packet (switch.hpp:266-303)                         */
+    NFCS_L2_NO_ETH = 3,         /* len < 14: ethernet() is null, the switch logs "unhandled" (328)       */
+    NFCS_L2_FLOOD = 4,          /* lookup_port misses (322-324); nothing further is tested               */
+    NFCS_L2_DROP_SAME_PORT = 5, /* on a hit, the first true term of the || chain at 314-316, in its order */
+    NFCS_L2_DROP_LINK_DOWN = 6,
+    NFCS_L2_DROP_STP = 7,
+    NFCS_L2_DROP_VLAN = 8       /* !should_forward(ingress, port, vlan): either port lacks a VLAN config,
+                                   or the VLAN's bit is clear in the ingress or the egress bitmap        */
+};
+/* What learn_mac(src_mac, ingress_port, vlan) would do (d_learn), for the frames the call decides (those
+ * not BAD_DESC, SKIP or NO_ETH; the others read NFCS_L2_LEARN_NONE). The table is NOT modified: the host
+ * applies the few NEW and MOVED entries and uploads again, which is how switch silicon reports learning. A
+ * batch of learn_mac calls from one port reaches the same table in any order, so nothing about order is
+ * lost. */
+enum {
+    NFCS_L2_LEARN_NONE = 0,    /* the entry is static: learn_mac leaves it                                */
+    NFCS_L2_LEARN_NEW = 1,     /* no entry exists                                                         */
+    NFCS_L2_LEARN_REFRESH = 2, /* a dynamic entry is already on the ingress port: only its timestamp      */
+    NFCS_L2_LEARN_MOVED = 3    /* a dynamic entry is on another port                                      */
+};
+
+typedef struct nfcs_fdb_entry { /* FdbEntry without its timestamp */
+    uint8_t mac[6];
+    uint16_t vlan_id;
+    uint32_t port;
+    uint8_t is_static;
+    uint8_t pad[3];
+} nfcs_fdb_entry;
+typedef struct nfcs_l2_port { /* one port's state as the L2 block reads it */
+    uint32_t port_id;
+    uint8_t link_up;         /* InterfaceManager::is_port_link_up                         */
+    uint8_t stp_forwarding;  /* get_port_stp_state(port) == PortState::FORWARDING         */
+    uint8_t has_vlan_config; /* VlanManager::get_port_config(port).has_value()            */
+    uint8_t type;            /* 0 ACCESS, 1 TRUNK, 2 HYBRID                               */
+    uint16_t native_vlan;
+    uint16_t pad;
+} nfcs_l2_port;
+#ifdef __cplusplus
+static_assert(sizeof(nfcs_fdb_entry) == 16, "nfcs_fdb_entry is a 16-byte record");
+static_assert(sizeof(nfcs_l2_port) == 12, "nfcs_l2_port is a 12-byte record");
+#endif
+
+#define NFCS_FDB_MAX_ENTRIES (1u << 20)
+#define NFCS_L2_MAX_PORTS 1024u
+
+/* The forwarding database and the port state the L2 block reads.
+ *   entries  pass ForwardingDatabase::get_all_entries() as it is. Of two entries with the same
+ *            (mac, vlan_id) the FIRST wins, as find_if returns the first (the reference itself never
+ *            holds duplicates). More than NFCS_FDB_MAX_ENTRIES: NFCS_EINVAL. 00:00:00:00:00:00 on VLAN
+ *            0 is a legal key: an empty slot is marked by a flag, not by a key value.
+ *   ports    one nfcs_fdb_set_port per port (the same id again replaces it); allowed_vlans is the
+ *            port's allowed set (NULL with n_allowed 0), ignored for ACCESS. port_id >=
+ *            NFCS_L2_MAX_PORTS, a native_vlan or an allowed VLAN above 4095, or a type above 2:
+ *            NFCS_EINVAL. A port never set, whatever its id (also one an FDB entry names), is the
+ *            reference's default: link down, STP UNKNOWN, no VLAN config. nfcs_fdb_clear_ports forgets
+ *            every port. Memory grows with the highest id set.
+ * nfcs_fdb_commit compiles
+ *   - the table: open addressing with linear probing over a power-of-two number of 16-byte slots
+ *     (16-byte aligned: one probe is one 16-byte load), at least 2 x entries and at least 16. A slot
+ *     holds the key, the port, an occupied flag and a static flag. commit records max_probe, the
+ *     longest displacement of any entry plus one: every search makes at most max_probe probes, and a
+ *     miss also ends at the first empty slot, so no loop depends on the table's contents alone to
+ *     end. The hash is one function compiled for host and device from one definition
+ *     (csrc/nfcs_fdb.h fdb_hash). Order carries no meaning (a key occurs once), so the table is
+ *     bit-exact with the reference's linear scan by construction. The device never writes it.
+ *   - per port one state byte and one 4096-bit VLAN bitmap: for ACCESS only the native VLAN's bit
+ *     (should_forward compares with native_vlan and ignores the set), for TRUNK and HYBRID the allowed
+ *     set, all zero without a VLAN config.
+ * Setters, commit and upload behave exactly as in nfcs_fib: a setter (set_entries, set_port,
+ * clear_ports) copies its input and invalidates an earlier commit, so nfcs_fdb_stats,
+ * nfcs_fdb_lookup_host and nfcs_fdb_flood_ports_host return NFCS_EINVAL until the next
+ * nfcs_fdb_commit; it does NOT invalidate an earlier upload, so nfcs_l2_lookup_device keeps serving
+ * the tables of the last nfcs_fdb_upload. The fdb must be destroyed before the ctx. */
+typedef struct nfcs_fdb nfcs_fdb;
+NFCS_API int nfcs_fdb_create(nfcs_fdb** out);
+NFCS_API int nfcs_fdb_destroy(nfcs_fdb* fdb); /* also frees what nfcs_fdb_upload allocated */
+NFCS_API int nfcs_fdb_set_entries(nfcs_fdb* fdb, const nfcs_fdb_entry* entries, uint32_t n);
+NFCS_API int nfcs_fdb_set_port(nfcs_fdb* fdb, const nfcs_l2_port* port, const uint16_t* allowed_vlans,
+                               uint32_t n_allowed);
+NFCS_API int nfcs_fdb_clear_ports(nfcs_fdb* fdb);
+NFCS_API int nfcs_fdb_commit(nfcs_fdb* fdb);
+/* Copies the committed tables to ctx's device (synchronous; replaces an earlier upload, which must no
+ * longer be in use). NFCS_EINVAL before nfcs_fdb_commit. */
+NFCS_API int nfcs_fdb_upload(nfcs_ctx* ctx, nfcs_fdb* fdb);
+/* The committed table: distinct entries, slots, max_probe, and `wrapped`, the number of entries whose
+ * probe sequence crossed from the last slot to slot 0 (each may be NULL). */
+NFCS_API int nfcs_fdb_stats(const nfcs_fdb* fdb, uint32_t* entries, uint32_t* slots, uint32_t* max_probe,
+                            uint32_t* wrapped);
+/* The decision for one frame received on ingress_port, on the CPU, from the same compiled arrays the
+ * kernel reads: *verdict = NFCS_L2_NO_ETH .. NFCS_L2_DROP_VLAN or NFCS_L2_FORWARD, *egress_port = the
+ * port for NFCS_L2_FORWARD, else NFCS_IF_NONE, *vlan = the VLAN used for the lookup (0 for
+ * NFCS_L2_NO_ETH), *learn = NFCS_L2_LEARN_* (each may be NULL). frame may be NULL when len is 0; no byte
+ * past 15 is read. */
+NFCS_API int nfcs_fdb_lookup_host(const nfcs_fdb* fdb, uint32_t ingress_port, const uint8_t* frame, uint32_t len,
+                                  uint32_t* verdict, uint32_t* egress_port, uint32_t* vlan, uint32_t* learn);
+/* flood_packet's port loop (switch.hpp:180-186) from the compiled port state: the ports i < num_ports
+ * with i != ingress_port, link up, STP forwarding and should_forward(ingress_port, i, vlan), ascending.
+ * *n = how many there are; the first min(cap, *n) go to ports (may be NULL when cap is 0). */
+NFCS_API int nfcs_fdb_flood_ports_host(const nfcs_fdb* fdb, uint32_t ingress_port, uint32_t vlan, uint32_t num_ports,
+                                       uint32_t* ports, uint32_t cap, uint32_t* n);
+
+/* Batched L2 decision over device-resident frames: one kernel, read-only on the frames (bytes 0..15 of
+ * each: the MACs, the EtherType and the TCI; `len >= 18` is a test of the length alone), asynchronous on
+ * the stream.
+ *   d_rt_verdict   optional (NULL) n bytes NFCS_RT_* from nfcs_route_lookup_device on the same burst:
+ *                  NFCS_RT_NOT_IPV4 is decided here, NFCS_RT_BAD_DESC reads NFCS_L2_BAD_DESC, every other
+ *                  value NFCS_L2_SKIP. NULL: every frame is decided here.
+ *   d_egress_port  n u32: the port for NFCS_L2_FORWARD, else NFCS_IF_NONE
+ *   d_verdict      optional (NULL) n bytes NFCS_L2_*
+ *   d_vlan         optional (NULL) n u16: the VLAN used for the lookup (0 where none was formed): TCI &
+ *                  0x0FFF when bytes 12-13 are 0x8100 and len >= 18, otherwise the ingress port's
+ *                  native_vlan, or 1 when that port has no VLAN config (PortConfig()'s default). A tagged
+ *                  frame of 14..17 bytes therefore uses the native VLAN (packet.hpp:609-617).
+ *   d_learn        optional (NULL) n bytes NFCS_L2_LEARN_*; NULL skips the source probe entirely
+ * n == 0 returns NFCS_OK without a launch. fdb must be uploaded to ctx (else NFCS_EINVAL) and stay
+ * unchanged until the call completes.
+ * ONE ingress port per call, for the reason given at nfcs_acl_eval_device: RX bursts arrive per port. */
+NFCS_API int nfcs_l2_lookup_device(nfcs_ctx* ctx, const nfcs_fdb* fdb, uint32_t ingress_port,
+                                   const uint8_t* d_arena, uint64_t arena_bytes, const nfcs_desc* d_desc,
+                                   uint32_t n, const uint8_t* d_rt_verdict, uint32_t* d_egress_port,
+                                   uint8_t* d_verdict, uint16_t* d_vlan, uint8_t* d_learn, void* stream);
+
 /* ---- VLAN push / pop + checksum ---------------------------------------- */
 
 /* One VLAN edit per packet as a u32: the operation in bits 30-31, the priority in bits 13-15

@@ -60,6 +60,19 @@ ACL_RULE_DTYPE = np.dtype([("fields", "<u4"), ("rule_id", "<u4"), ("src_mac", "u
                            ("protocol", "u1"), ("action", "u1"), ("pad", "u1", (2,)), ("redirect_port", "<u4")])
 assert ACL_RULE_DTYPE.itemsize == 52
 
+# nfcs_l2_lookup_device / nfcs_fdb_lookup_host (include/nfcs.h NFCS_L2_*)
+(L2_FORWARD, L2_BAD_DESC, L2_SKIP, L2_NO_ETH, L2_FLOOD, L2_DROP_SAME_PORT, L2_DROP_LINK_DOWN, L2_DROP_STP,
+ L2_DROP_VLAN) = range(9)
+L2_LEARN_NONE, L2_LEARN_NEW, L2_LEARN_REFRESH, L2_LEARN_MOVED = range(4)
+L2_ACCESS, L2_TRUNK, L2_HYBRID = range(3)  # nfcs_l2_port.type
+FDB_MAX_ENTRIES = 1 << 20
+L2_MAX_PORTS = 1024
+FDB_ENTRY_DTYPE = np.dtype([("mac", "u1", (6,)), ("vlan_id", "<u2"), ("port", "<u4"), ("is_static", "u1"),
+                            ("pad", "u1", (3,))])
+L2_PORT_DTYPE = np.dtype([("port_id", "<u4"), ("link_up", "u1"), ("stp_forwarding", "u1"), ("has_vlan_config", "u1"),
+                          ("type", "u1"), ("native_vlan", "<u2"), ("pad", "<u2")])
+assert FDB_ENTRY_DTYPE.itemsize == 16 and L2_PORT_DTYPE.itemsize == 12
+
 NEXTHOP_DTYPE = np.dtype([("dst_mac", "u1", (6,)), ("src_mac", "u1", (6,))])
 FLOW_KEY_DTYPE = np.dtype([("hash", "<u4"), ("vlan_id", "<u2"), ("ethertype", "<u2"),
                            ("src_mac", "u1", (6,)), ("dst_mac", "u1", (6,)), ("protocol", "u1"),
@@ -167,6 +180,18 @@ def _declare(L):
         "nfcs_acl_eval_host": ([_vp, _vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32),
                                 ctypes.POINTER(_u32)], ctypes.c_int),
         "nfcs_acl_eval_device": ([_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+        "nfcs_fdb_create": ([ctypes.POINTER(_vp)], ctypes.c_int),
+        "nfcs_fdb_destroy": ([_vp], ctypes.c_int),
+        "nfcs_fdb_set_entries": ([_vp, _vp, _u32], ctypes.c_int),
+        "nfcs_fdb_set_port": ([_vp, _vp, _vp, _u32], ctypes.c_int),
+        "nfcs_fdb_clear_ports": ([_vp], ctypes.c_int),
+        "nfcs_fdb_commit": ([_vp], ctypes.c_int),
+        "nfcs_fdb_upload": ([_vp, _vp], ctypes.c_int),
+        "nfcs_fdb_stats": ([_vp] + [ctypes.POINTER(_u32)] * 4, ctypes.c_int),
+        "nfcs_fdb_lookup_host": ([_vp, _u32, _vp, _u32] + [ctypes.POINTER(_u32)] * 4, ctypes.c_int),
+        "nfcs_fdb_flood_ports_host": ([_vp, _u32, _u32, _u32, _vp, _u32, ctypes.POINTER(_u32)], ctypes.c_int),
+        "nfcs_l2_lookup_device": ([_vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp],
+                                  ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         # a measurement build of an earlier round (NFCS_LIB, A/B runs) may lack a later entry point;
@@ -345,6 +370,90 @@ class Acl:
     def close(self):
         if getattr(self, "ptr", None):
             lib().nfcs_acl_destroy(self.ptr)
+            self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Fdb:
+    """The L2 forwarding database and port state behind Engine.l2_lookup_device (nfcs_fdb): FDB_ENTRY_DTYPE
+    records (pass ForwardingDatabase::get_all_entries() as it is; of two with one (mac, vlan_id) the first
+    wins), compiled into an open-addressing hash table, and one L2_PORT_DTYPE record plus allowed VLANs per
+    port. A port never set is link down, STP unknown, without a VLAN config."""
+
+    def __init__(self):
+        p = _vp()
+        _check(lib().nfcs_fdb_create(ctypes.byref(p)), "nfcs_fdb_create")
+        self.ptr = p.value
+
+    def set_entries(self, entries):
+        """FDB_ENTRY_DTYPE records; at most FDB_MAX_ENTRIES."""
+        entries = np.ascontiguousarray(entries, dtype=FDB_ENTRY_DTYPE)
+        _check(lib().nfcs_fdb_set_entries(self.ptr, entries.ctypes.data if len(entries) else None, len(entries)),
+               "nfcs_fdb_set_entries")
+        return self
+
+    def set_port(self, port_id: int, link_up=True, stp_forwarding=True, has_vlan_config=True, type=L2_ACCESS,
+                 native_vlan: int = 1, allowed_vlans=()):
+        """One port's state (nfcs_l2_port) and, for L2_TRUNK / L2_HYBRID, its allowed VLANs."""
+        rec = np.zeros(1, dtype=L2_PORT_DTYPE)
+        rec["port_id"], rec["link_up"], rec["stp_forwarding"] = port_id, bool(link_up), bool(stp_forwarding)
+        rec["has_vlan_config"], rec["type"], rec["native_vlan"] = bool(has_vlan_config), type, native_vlan
+        allowed = np.ascontiguousarray(list(allowed_vlans), dtype=np.uint16)
+        _check(lib().nfcs_fdb_set_port(self.ptr, rec.ctypes.data, allowed.ctypes.data if len(allowed) else None,
+                                       len(allowed)), "nfcs_fdb_set_port")
+        return self
+
+    def clear_ports(self):
+        _check(lib().nfcs_fdb_clear_ports(self.ptr), "nfcs_fdb_clear_ports")
+        return self
+
+    def commit(self):
+        _check(lib().nfcs_fdb_commit(self.ptr), "nfcs_fdb_commit")
+        return self
+
+    def upload(self, engine: "Engine"):
+        """Copy the committed tables to the engine's device; close the Fdb before the engine."""
+        _check(lib().nfcs_fdb_upload(engine.ctx, self.ptr), "nfcs_fdb_upload")
+        return self
+
+    def stats(self) -> dict:
+        """The committed table: entries (distinct keys), slots, max_probe (longest displacement + 1) and
+        wrapped (entries whose probe sequence crossed from the last slot to slot 0)."""
+        v = [_u32() for _ in range(4)]
+        _check(lib().nfcs_fdb_stats(self.ptr, *(ctypes.byref(x) for x in v)), "nfcs_fdb_stats")
+        return dict(zip(("entries", "slots", "max_probe", "wrapped"), (int(x.value) for x in v)))
+
+    def lookup_host(self, ingress_port: int, frame: bytes) -> tuple[int, int, int, int]:
+        """(verdict L2_*, egress port or IF_NONE, VLAN used for the lookup, learn class L2_LEARN_*) for one
+        frame received on ingress_port, on the CPU, from the arrays the kernel reads."""
+        v = [_u32() for _ in range(4)]
+        frame = bytes(frame)
+        _check(lib().nfcs_fdb_lookup_host(self.ptr, int(ingress_port), frame if frame else None, len(frame),
+                                          *(ctypes.byref(x) for x in v)), "nfcs_fdb_lookup_host")
+        return tuple(int(x.value) for x in v)
+
+    def flood_ports_host(self, ingress_port: int, vlan: int, num_ports: int) -> np.ndarray:
+        """flood_packet's port list for a frame received on ingress_port on `vlan`, ascending."""
+        n = _u32()
+        out = np.zeros(max(num_ports, 1), dtype=np.uint32)
+        _check(lib().nfcs_fdb_flood_ports_host(self.ptr, int(ingress_port), int(vlan), int(num_ports), out.ctypes.data,
+                                               len(out), ctypes.byref(n)), "nfcs_fdb_flood_ports_host")
+        return out[:n.value].copy()
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            lib().nfcs_fdb_destroy(self.ptr)
             self.ptr = None
 
     def __enter__(self):
@@ -540,6 +649,18 @@ class Engine:
         ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
         _check(lib().nfcs_acl_eval_device(self.ctx, acl.ptr, ptr(arena), arena_bytes, ptr(desc), n, ptr(action),
                                           ptr(rule), ptr(redirect), ptr(nh), stream), "nfcs_acl_eval_device")
+
+    def l2_lookup_device(self, fdb: "Fdb", ingress_port: int, arena, arena_bytes: int, desc, n: int, egress_port,
+                         rt_verdict=None, verdict=None, vlan=None, learn=None, stream=None):
+        """The switch's L2 decision per frame received on ingress_port (FDB lookup, same-port / link / STP /
+        VLAN checks, flood on a miss) on device frames, read-only: egress_port = n u32 (the port for
+        L2_FORWARD, else IF_NONE); rt_verdict (n bytes RT_* of route_lookup_device on the same burst: only
+        RT_NOT_IPV4 frames are decided, the rest read L2_SKIP), verdict (n bytes L2_*), vlan (n u16: the
+        VLAN used for the lookup) and learn (n bytes L2_LEARN_*; None skips the source probe) optional."""
+        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
+        _check(lib().nfcs_l2_lookup_device(self.ctx, fdb.ptr, int(ingress_port), ptr(arena), arena_bytes, ptr(desc), n,
+                                           ptr(rt_verdict), ptr(egress_port), ptr(verdict), ptr(vlan), ptr(learn),
+                                           stream), "nfcs_l2_lookup_device")
 
     def vlan_device(self, arena, arena_bytes: int, desc, n: int, ops=None, op_all: int = 0,
                     caps=None, cap_all: int = 0, status=None, stream=None):

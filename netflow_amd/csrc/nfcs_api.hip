@@ -1238,6 +1238,169 @@ NFCS_API int nfcs_acl_eval_device(nfcs_ctx* c, const nfcs_acl* a, const uint8_t*
     return NFCS_OK;
 }
 
+// ---- L2 forwarding database (nfcs_fdb.h: compile, host decision) and its lookup kernel -----------
+}  // extern "C"
+
+struct nfcs_fdb {
+    nfcs::FdbInputs in;
+    nfcs::FdbTables t;
+    bool committed = false;
+    // nfcs_fdb_upload: one device allocation holding every array, on `device`
+    int device = -1;
+    uint8_t* d_blob = nullptr;
+    nfcs::FdbDev dev;
+    bool uploaded = false;
+};
+
+namespace {
+void fdb_drop_upload(nfcs_fdb* f) {
+    if (f->d_blob) {
+        DeviceGuard dg_(f->device);
+        if (dg_.err == hipSuccess) (void)hipFree(f->d_blob);
+    }
+    f->d_blob = nullptr;
+    f->dev = nfcs::FdbDev{};
+    f->uploaded = false;
+}
+}  // namespace
+
+extern "C" {
+
+NFCS_API int nfcs_fdb_create(nfcs_fdb** out) {
+    if (!out) return NFCS_EINVAL;
+    *out = new (std::nothrow) nfcs_fdb();
+    return *out ? NFCS_OK : NFCS_ENOMEM;
+}
+
+NFCS_API int nfcs_fdb_destroy(nfcs_fdb* f) {
+    if (!f) return NFCS_EINVAL;
+    fdb_drop_upload(f);
+    delete f;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_fdb_set_entries(nfcs_fdb* f, const nfcs_fdb_entry* entries, uint32_t n) {
+    if (!f || (n > 0 && !entries) || n > NFCS_FDB_MAX_ENTRIES) return NFCS_EINVAL;
+    try {
+        f->in.entries.assign(entries, entries + n);
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+    f->committed = false;  // the device copy, if any, stays as it is until the next upload
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_fdb_set_port(nfcs_fdb* f, const nfcs_l2_port* port, const uint16_t* allowed_vlans,
+                               uint32_t n_allowed) {
+    if (!f || !port || (n_allowed > 0 && !allowed_vlans)) return NFCS_EINVAL;
+    if (port->port_id >= NFCS_L2_MAX_PORTS || port->native_vlan > 4095u || port->type > 2u) return NFCS_EINVAL;
+    for (uint32_t i = 0; i < n_allowed; ++i)
+        if (allowed_vlans[i] > 4095u) return NFCS_EINVAL;
+    try {
+        if (f->in.ports.size() <= port->port_id) f->in.ports.resize(port->port_id + 1u);
+        nfcs::FdbPortIn& pi = f->in.ports[port->port_id];
+        pi.allowed.assign(allowed_vlans, allowed_vlans + n_allowed);
+        pi.port = *port;
+        pi.set = true;
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+    f->committed = false;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_fdb_clear_ports(nfcs_fdb* f) {
+    if (!f) return NFCS_EINVAL;
+    f->in.ports.clear();
+    f->committed = false;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_fdb_commit(nfcs_fdb* f) {
+    if (!f) return NFCS_EINVAL;
+    try {
+        nfcs::fdb_compile(f->in, f->t);
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+    f->committed = true;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_fdb_upload(nfcs_ctx* c, nfcs_fdb* f) {
+    if (!c || !f || !f->committed) return NFCS_EINVAL;
+    fdb_drop_upload(f);
+    DeviceGuard dg_(c->di.device);
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    const nfcs::FdbTables& t = f->t;
+    // one blob, every array on a 16-byte boundary: the slots first (hipMalloc aligns them)
+    auto up16 = [](size_t x) { return (x + 15u) & ~size_t(15); };
+    const size_t b_slots = t.slots.size() * sizeof(nfcs::FdbSlot), b_vlans = t.port_vlans.size() * 4u;
+    const size_t o_vlans = b_slots, o_native = o_vlans + up16(b_vlans), o_state = o_native + up16(t.ports * 2u);
+    const size_t total = o_state + up16(t.ports) + 16u;
+    NFCS_HIP(hipMalloc(&f->d_blob, total));
+    f->device = c->di.device;
+    hipError_t e = hipMemset(f->d_blob, 0, total);
+    if (e == hipSuccess) e = hipMemcpy(f->d_blob, t.slots.data(), b_slots, hipMemcpyHostToDevice);
+    if (e == hipSuccess && t.ports) {
+        e = hipMemcpy(f->d_blob + o_vlans, t.port_vlans.data(), b_vlans, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(f->d_blob + o_native, t.port_native.data(), t.ports * 2u, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(f->d_blob + o_state, t.port_state.data(), t.ports, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        fdb_drop_upload(f);
+        return hip_fail(e);
+    }
+    f->dev.slots = (const uint4*)f->d_blob;
+    f->dev.slot_mask = (uint32_t)t.slots.size() - 1u;
+    f->dev.max_probe = t.max_probe;
+    f->dev.port_vlans = (const uint32_t*)(f->d_blob + o_vlans);
+    f->dev.port_native = (const uint16_t*)(f->d_blob + o_native);
+    f->dev.port_state = f->d_blob + o_state;
+    f->dev.ports = t.ports;
+    f->uploaded = true;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_fdb_stats(const nfcs_fdb* f, uint32_t* entries, uint32_t* slots, uint32_t* max_probe,
+                            uint32_t* wrapped) {
+    if (!f || !f->committed) return NFCS_EINVAL;
+    if (entries) *entries = f->t.entries;
+    if (slots) *slots = (uint32_t)f->t.slots.size();
+    if (max_probe) *max_probe = f->t.max_probe;
+    if (wrapped) *wrapped = f->t.wrapped;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_fdb_lookup_host(const nfcs_fdb* f, uint32_t ingress_port, const uint8_t* frame, uint32_t len,
+                                  uint32_t* verdict, uint32_t* egress_port, uint32_t* vlan, uint32_t* learn) {
+    if (!f || !f->committed || (len > 0 && !frame)) return NFCS_EINVAL;
+    nfcs::fdb_decide(f->t, ingress_port, frame, len, verdict, egress_port, vlan, learn);
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_fdb_flood_ports_host(const nfcs_fdb* f, uint32_t ingress_port, uint32_t vlan, uint32_t num_ports,
+                                       uint32_t* ports, uint32_t cap, uint32_t* n) {
+    if (!f || !f->committed || !n || (cap > 0 && !ports)) return NFCS_EINVAL;
+    *n = nfcs::fdb_flood_ports(f->t, ingress_port, vlan, num_ports, ports, cap);
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_l2_lookup_device(nfcs_ctx* c, const nfcs_fdb* f, uint32_t ingress_port, const uint8_t* d_arena,
+                                   uint64_t arena_bytes, const nfcs_desc* d_desc, uint32_t n,
+                                   const uint8_t* d_rt_verdict, uint32_t* d_egress_port, uint8_t* d_verdict,
+                                   uint16_t* d_vlan, uint8_t* d_learn, void* stream) {
+    if (!c || !f || !f->uploaded || f->device != c->di.device) return NFCS_EINVAL;
+    DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    if (n == 0) return NFCS_OK;
+    if (!d_arena || !d_desc || !d_egress_port || ((uintptr_t)d_arena & 15u)) return NFCS_EINVAL;
+    if (((uintptr_t)d_egress_port & 3u) || ((uintptr_t)d_vlan & 1u)) return NFCS_EINVAL;
+    NFCS_HIP(nfcs::launch_l2_lookup(c->di, f->dev, ingress_port, d_arena, arena_bytes, d_desc, n, d_rt_verdict,
+                                    d_egress_port, d_verdict, d_vlan, d_learn, pick(c, stream)));
+    return NFCS_OK;
+}
+
 NFCS_API int nfcs_update_host(nfcs_ctx* c, uint8_t* h_arena, uint64_t arena_bytes,
                               const nfcs_desc* h_desc, uint32_t n, uint8_t* h_status,
                               uint32_t flags) {

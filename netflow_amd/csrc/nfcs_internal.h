@@ -7,6 +7,7 @@
 
 #include "nfcs.h"
 #include "nfcs_acl.h"
+#include "nfcs_fdb.h"
 #include "nfcs_fib.h"
 
 namespace nfcs {
@@ -211,6 +212,21 @@ struct AclDev {
 hipError_t launch_acl_eval(const DevInfo& di, const AclDev& acl, const uint8_t* arena, uint64_t arena_bytes,
                            const nfcs_desc* desc, uint32_t n, uint8_t* action, uint32_t* rule, uint32_t* redirect,
                            uint32_t* nh, hipStream_t stream);
+
+// The committed L2 tables in device memory (nfcs_fdb_upload; the arrays of FdbTables, nfcs_fdb.h).
+struct FdbDev {
+    const uint4* slots = nullptr;          // slot_mask + 1 16-byte slots {k0, k1, port, flags}, 16-byte aligned
+    uint32_t slot_mask = 0, max_probe = 0;
+    const uint8_t* port_state = nullptr;   // ports state bytes kL2*
+    const uint16_t* port_native = nullptr; // ports native VLANs
+    const uint32_t* port_vlans = nullptr;  // ports x kL2VlanWords bitmap words
+    uint32_t ports = 0;
+};
+
+hipError_t launch_l2_lookup(const DevInfo& di, const FdbDev& fdb, uint32_t ingress, const uint8_t* arena,
+                            uint64_t arena_bytes, const nfcs_desc* desc, uint32_t n, const uint8_t* rt_verdict,
+                            uint32_t* egress_port, uint8_t* verdict, uint16_t* vlan, uint8_t* learn,
+                            hipStream_t stream);
 
 hipError_t launch_gen_config(const DevInfo& di, int config, uint64_t seed, uint64_t first,
                              uint32_t n, uint8_t* arena, uint64_t arena_bytes,

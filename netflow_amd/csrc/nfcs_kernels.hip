@@ -2400,6 +2400,131 @@ hipError_t launch_acl_eval(const DevInfo& di, const AclDev& acl, const uint8_t* 
     return hipGetLastError();
 }
 
+// ---- L2 forwarding: FDB lookup, port / VLAN checks, learning -------------------
+// The L2 block of the switch (switch.hpp:305-326) per packet: a wave takes 64 packets, one lane each,
+// with route_lookup_kernel's descriptor load, liveness test and XCD-aware block order. Everything the
+// block reads of a frame — both MACs, the EtherType and the TCI — lies in bytes 0..15, so lane l loads
+// that one 16-byte chunk of packet l itself (non-temporal: the frames are streamed) and no LDS is
+// used. The table (nfcs_fdb.h FdbSlot) is probed per lane from global memory with the default cache
+// policy (it is the reused data): the destination's and the source's probe sequences advance together,
+// two independent 16-byte loads per lane per trip issued from one block, so that both are in flight
+// before the first is used. A lane that has finished both searches issues no loads (a wave makes as many
+// trips as its slowest lane: with every lane loading on every trip the kernel took up to four times as
+// long). The wave leaves the loop once no lane is still searching, after max_probe trips
+// at the latest; a lane's search also ends at an empty slot (nfcs_fdb.h fdb_find is the same loop). Every
+// slot index is masked into the table. LEARN = false (d_learn NULL) compiles the source probe out.
+
+// One slot of a probe sequence: fdb_find's loop body.
+DEV void fdb_step(const uint4& s, uint32_t k0, uint32_t k1, bool& search, bool& hit, uint32_t& port, uint32_t& flags) {
+    const bool occ = (s.w & kFdbOccupied) != 0, m = search && occ && s.x == k0 && s.y == k1;
+    port = m ? s.z : port;
+    flags = m ? s.w : flags;
+    hit = hit || m;
+    search = search && !m && occ;
+}
+
+template <bool LEARN>
+__global__ __launch_bounds__(kBlock) void l2_lookup_kernel(const nfcs_desc* __restrict__ desc, uint32_t n,
+                                                           uint32_t nblocks, const uint8_t* __restrict__ arena,
+                                                           uint64_t arena_bytes, const FdbDev fdb, uint32_t ingress,
+                                                           const uint8_t* __restrict__ rt_verdict,
+                                                           uint32_t* __restrict__ port_out,
+                                                           uint8_t* __restrict__ verdict_out,
+                                                           uint16_t* __restrict__ vlan_out,
+                                                           uint8_t* __restrict__ learn_out) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t p0 = ((uint64_t)xcd_block_n(nblocks) * kWavesPerBlock + rfl(wave)) * 64u;
+    if (p0 >= n) return;
+    // lane l: descriptor of packet p0 + l (one coalesced load); dead packets read as length 0
+    const uint64_t p = p0 + lane;
+    uint2 dl = make_uint2(0u, 0u);
+    uint32_t rtv = NFCS_RT_NOT_IPV4;
+    if (p < n) {
+        dl = ((const uint2*)desc)[p];
+        if (rt_verdict) rtv = rt_verdict[p];
+    }
+    const uint64_t off = (uint64_t)dl.x * 16u;
+    const bool live = p < n && off + (((uint64_t)dl.y + 15u) & ~15ull) <= arena_bytes && rtv != NFCS_RT_BAD_DESC;
+    const bool mine = live && rtv == NFCS_RT_NOT_IPV4;  // else the L3 block took the packet
+    const uint32_t len = mine ? dl.y : 0u;
+    const bool eth = len >= 14u;  // the frame's first chunk lies inside the arena: len > 0 and live
+    const uint4 c = ld16<1>(eth ? (const uint4*)(arena + off) : g_zero_line);
+    // the ingress port's state: wave-uniform
+    const bool in_known = ingress < fdb.ports;
+    const uint32_t native = in_known ? fdb.port_native[ingress] : kL2DefaultVlan;
+    const uint32_t* in_vlans = fdb.port_vlans + (size_t)(in_known ? ingress : 0u) * kL2VlanWords;
+    // bytes 12-13 = 0x8100 and len >= 18: TCI & 0x0FFF (Packet::vlan_id), else the native VLAN
+    const bool tagged = (c.w & 0xFFFFu) == 0x0081u && len >= 18u;
+    const uint32_t vlan = !eth ? 0u : tagged ? (bswap16(c.w >> 16) & 0x0FFFu) : native;
+    const uint32_t dk0 = c.x, dk1 = (c.y & 0xFFFFu) | (vlan << 16);
+    const uint32_t sk0 = (c.y >> 16) | (c.z << 16), sk1 = (c.z >> 16) | (vlan << 16);
+    const uint32_t mask = fdb.slot_mask;
+    const uint32_t dh = fdb_hash(dk0, dk1), sh = fdb_hash(sk0, sk1);
+    bool dsearch = eth, ssearch = LEARN && eth, dhit = false, shit = false;
+    uint32_t dport = 0, dflags = 0, sport = 0, sflags = 0;
+    for (uint32_t i = 0; i < fdb.max_probe; ++i) {
+        if (__builtin_amdgcn_ballot_w64(dsearch || ssearch) == 0) break;
+        uint4 ds = make_uint4(0u, 0u, 0u, 0u), ss = ds;
+        if (dsearch || ssearch) {  // one block: both loads are in flight before the first use
+            ds = fdb.slots[(dh + i) & mask];
+            if (LEARN) ss = fdb.slots[(sh + i) & mask];
+        }
+        fdb_step(ds, dk0, dk1, dsearch, dhit, dport, dflags);
+        if (LEARN) fdb_step(ss, sk0, sk1, ssearch, shit, sport, sflags);
+    }
+    // on a hit, the || chain of switch.hpp:314-316 in its order
+    uint32_t v = !live ? (uint32_t)NFCS_L2_BAD_DESC
+               : !mine ? (uint32_t)NFCS_L2_SKIP
+               : !eth  ? (uint32_t)NFCS_L2_NO_ETH
+                       : (uint32_t)NFCS_L2_FLOOD;
+    uint32_t eg = NFCS_IF_NONE;
+    if (dhit) {
+        const bool known = dport < fdb.ports;  // a port never set: link down
+        const uint32_t st = known ? fdb.port_state[dport] : 0u;
+        const uint32_t w = vlan >> 5, bit = 1u << (vlan & 31u);  // vlan <= 4095: w < kL2VlanWords
+        const uint32_t in_w = in_known ? in_vlans[w] : 0u;
+        const uint32_t eg_w = known ? fdb.port_vlans[(size_t)dport * kL2VlanWords + w] : 0u;
+        if (dport == ingress) v = NFCS_L2_DROP_SAME_PORT;
+        else if (!(st & kL2LinkUp)) v = NFCS_L2_DROP_LINK_DOWN;
+        else if (!(st & kL2StpFwd)) v = NFCS_L2_DROP_STP;
+        else if (!(in_w & eg_w & bit)) v = NFCS_L2_DROP_VLAN;
+        else {
+            v = NFCS_L2_FORWARD;
+            eg = dport;
+        }
+    }
+    if (p < n) {  // one packet per lane: each store instruction writes consecutive elements
+        port_out[p] = eg;
+        if (verdict_out) verdict_out[p] = (uint8_t)v;
+        if (vlan_out) vlan_out[p] = (uint16_t)vlan;
+        if (LEARN) {
+            const uint32_t learn = !eth                  ? (uint32_t)NFCS_L2_LEARN_NONE
+                                 : !shit                 ? (uint32_t)NFCS_L2_LEARN_NEW
+                                 : (sflags & kFdbStatic) ? (uint32_t)NFCS_L2_LEARN_NONE
+                                 : sport == ingress      ? (uint32_t)NFCS_L2_LEARN_REFRESH
+                                                         : (uint32_t)NFCS_L2_LEARN_MOVED;
+            learn_out[p] = (uint8_t)learn;
+        }
+    }
+}
+
+hipError_t launch_l2_lookup(const DevInfo& di, const FdbDev& fdb, uint32_t ingress, const uint8_t* arena,
+                            uint64_t arena_bytes, const nfcs_desc* desc, uint32_t n, const uint8_t* rt_verdict,
+                            uint32_t* egress_port, uint8_t* verdict, uint16_t* vlan, uint8_t* learn,
+                            hipStream_t stream) {
+    (void)di;
+    if (n == 0) return hipSuccess;
+    // 64 packets per wave, one lane each, XCD-aware order; no LDS
+    const uint32_t g = (n + 255u) / 256u;
+    if (learn)
+        hipLaunchKernelGGL(l2_lookup_kernel<true>, dim3(g), dim3(kBlock), 0, stream, desc, n, g, arena, arena_bytes, fdb,
+                           ingress, rt_verdict, egress_port, verdict, vlan, learn);
+    else
+        hipLaunchKernelGGL(l2_lookup_kernel<false>, dim3(g), dim3(kBlock), 0, stream, desc, n, g, arena, arena_bytes, fdb,
+                           ingress, rt_verdict, egress_port, verdict, vlan, learn);
+    return hipGetLastError();
+}
+
 // ---- synthetic config generator (same spec as oracle/nfcs_oracle.c) -----------
 constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
 __host__ __device__ inline uint64_t mix64(uint64_t z) {
