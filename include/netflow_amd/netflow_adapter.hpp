@@ -25,6 +25,9 @@
 //   fdb.lookup_port, the same-port / link /   netflow_amd::l2_lookup_batch(pkts, fdb, ingress_port, egress_port[,
 //   STP / should_forward checks, flood        verdict, vlan, learn, rt_verdict]) with fdb = netflow_amd::make_fdb(
 //        switch.hpp:305-326                   fdb, vlan_manager, link_up, stp_forwarding, num_ports)
+//   vlan_manager.process_egress(pkt, port) +  netflow_amd::egress_plan_batch(pkts, eg, egress_port, ops, queue), then
+//   qos_manager.enqueue_packet(pkt, port)     vlan_batch(pkts, ops) and egress_enqueue_batch(eg, egress_port, queue, ...)
+//        switch.hpp:113-139                   with eg = netflow_amd::make_egress(vlan_manager, qos_manager, num_ports)
 //
 // Every entry returns 0 or a negative NFCS_E* code and never throws (the reference's calls are
 // void / bool and never throw); per-packet outcomes are the NFCS_ST_* status bytes. The bytes
@@ -49,7 +52,8 @@ namespace netflow {
 class RoutingManager;  // <netflow++/routing_manager.hpp>, for make_fib below
 struct AclRule;        // <netflow++/acl_manager.hpp>, for make_acl below
 class ForwardingDatabase;  // <netflow++/forwarding_database.hpp>, for make_fdb below
-class VlanManager;         // <netflow++/vlan_manager.hpp>, for make_fdb below
+class VlanManager;         // <netflow++/vlan_manager.hpp>, for make_fdb and make_egress below
+class QosManager;          // <netflow++/qos_manager.hpp>, for make_egress below
 }
 
 namespace netflow_amd {
@@ -171,6 +175,29 @@ template <class ForwardingDatabaseT = netflow::ForwardingDatabase, class VlanMan
 inline int make_fdb(const ForwardingDatabaseT& fdb, const VlanManagerT& vlans, LinkUp&& link_up,
                     StpForwarding&& stp_forwarding, uint32_t num_ports, nfcs_fdb** out) {
     return make_fdb_from(fdb, vlans, link_up, stp_forwarding, num_ports, out);
+}
+
+inline int egress_plan_batch(netflow::Packet* const* pkts, size_t n, const nfcs_egress* eg, const uint32_t* egress_port,
+                             uint32_t* ops, uint8_t* queue) {
+    return detail::on_default_engine(
+        [&](ChecksumEngine& e) { return e.egress_plan_batch(pkts, n, eg, egress_port, ops, queue); });
+}
+inline int egress_plan_batch(const std::vector<netflow::Packet*>& pkts, const nfcs_egress* eg,
+                             const uint32_t* egress_port, uint32_t* ops, uint8_t* queue) {
+    return egress_plan_batch(pkts.data(), pkts.size(), eg, egress_port, ops, queue);
+}
+
+// Committed egress ports (nfcs_egress) from the switch's own state: for the ports 0 .. num_ports - 1
+// VlanManager::get_port_config (type, native_vlan, tag_native) and QosManager::get_port_qos_config
+// (num_queues, max_queue_depth, as configure_port_qos normalised them). Returns NFCS_OK and the object in
+// *out (nfcs_egress_destroy it; upload it with ChecksumEngine::upload_egress before egress_plan_batch), or a
+// negative NFCS_E* code. A template, so that <netflow++/vlan_manager.hpp> and <netflow++/qos_manager.hpp>
+// are needed only where make_egress is used: the caller includes them and links vlan_manager.cpp and
+// qos_manager.cpp. The work is netflow_amd::make_egress_from (packet.hpp), which any types with the same
+// member names can use.
+template <class VlanManagerT = netflow::VlanManager, class QosManagerT = netflow::QosManager>
+inline int make_egress(const VlanManagerT& vlans, const QosManagerT& qos, uint32_t num_ports, nfcs_egress** out) {
+    return make_egress_from(vlans, qos, num_ports, out);
 }
 
 // On an engine of the caller's (another device; one engine per GPU, one host thread each).

@@ -26,6 +26,11 @@
 // the switch's L2 data plane (switch.hpp:305-326) for a burst, from a database built by make_fdb_from
 //   netflow_amd::l2_lookup_batch(Packet* const*, size_t, const nfcs_fdb*, ingress_port, egress_port, ...)
 // (nfcs_l2_lookup_device: FDB lookup, same-port / link / STP / VLAN checks, flood, learn classes).
+// The egress stage (Switch::process_egress_pipeline, switch.hpp:113-139) from ports built by make_egress_from
+//   netflow_amd::egress_plan_batch(Packet* const*, size_t, const nfcs_egress*, egress_port, ops, queue)
+//   netflow_amd::egress_enqueue_batch(const nfcs_egress*, port, queue, n, depth, result, order, key_start, ...)
+// (nfcs_egress_plan_device: the VLAN edit and the queue per packet; nfcs_egress_enqueue_device: per
+// (port, queue) the packet indexes in arrival order, tail drops counted).
 //
 // The batch entry points are templates over the packet type: they take this header's Packet or
 // the reference's own netflow::Packet (include/netflow_amd/netflow_adapter.hpp), whose buffers
@@ -262,6 +267,28 @@ public:
     int upload_fdb(nfcs_fdb* fdb) {
         std::lock_guard<std::mutex> lock(mu_);
         return nfcs_fdb_upload(ctx_, fdb);
+    }
+
+    // The egress decision (VlanManager::process_egress + QosManager::classify_packet_to_queue) for a batch
+    // whose packet i leaves through egress_port[i] (NFCS_IF_NONE: none), from committed egress ports
+    // (nfcs_egress_*; upload_egress first): ops[i] = NFCS_VLAN_POP or NFCS_VLAN_NOP (what process_egress
+    // does to the packet), queue[i] = the queue of the packet as it is after that edit, NFCS_QUEUE_NONE
+    // without a port. Reads bytes 12..19 of each packet; the packets are not changed.
+    template <class Pkt>
+    int egress_plan_batch(Pkt* const* pkts, size_t n, const nfcs_egress* eg, const uint32_t* egress_port,
+                          uint32_t* ops, uint8_t* queue);
+    // QosManager::enqueue_packet for a burst (nfcs_egress_enqueue_device; host arrays, copied in and out):
+    // port[i] and queue[i] as egress_plan_batch gives them, depth = one u32 per key (nfcs_egress_keys), in /
+    // out; order (n u32, the first key_start[keys] are written), key_start (keys + 1 u32); result (n bytes
+    // NFCS_EQ_*) and key_dropped (keys u32) optional.
+    int egress_enqueue_batch(const nfcs_egress* eg, const uint32_t* port, const uint8_t* queue, size_t n,
+                             uint32_t* depth, uint8_t* result, uint32_t* order, uint32_t* key_start,
+                             uint32_t* key_dropped = nullptr);
+    // nfcs_egress_upload to this engine's device, serialised with its other calls. The object must be
+    // destroyed before the engine.
+    int upload_egress(nfcs_egress* eg) {
+        std::lock_guard<std::mutex> lock(mu_);
+        return nfcs_egress_upload(ctx_, eg);
     }
 
     nfcs_ctx* ctx() const { return ctx_; }
@@ -682,6 +709,67 @@ int ChecksumEngine::l2_lookup_batch(Pkt* const* pkts, size_t n, const nfcs_fdb* 
     return NFCS_OK;
 }
 
+template <class Pkt>
+int ChecksumEngine::egress_plan_batch(Pkt* const* pkts, size_t n, const nfcs_egress* eg, const uint32_t* egress_port,
+                                      uint32_t* ops, uint8_t* queue) {
+    if (n == 0) return NFCS_OK;
+    if (!pkts || !eg || !egress_port || !ops || !queue || n > 0xFFFFFFFFu) return NFCS_EINVAL;
+    std::lock_guard<std::mutex> lock(mu_);
+    // gather clamps each length to 32: the decision tests lengths against 14, 18 and 22 only
+    int rc = reserve(n * 32 + 16, n);
+    if (rc) return rc;
+    const size_t off = gather(pkts, n, 32);
+    DevTmp din(ctx_, n * sizeof(uint32_t), rc);
+    DevTmp dport(ctx_, n * sizeof(uint32_t), rc);
+    DevTmp dops(ctx_, n * sizeof(uint32_t), rc);
+    if (rc) return rc;
+    const uint32_t m = static_cast<uint32_t>(n);
+    if ((rc = nfcs_memcpy_h2d(ctx_, d_arena_, h_arena_, off ? off : 16))) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, d_desc_, h_desc_, n * sizeof(nfcs_desc)))) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, din.p, egress_port, n * sizeof(uint32_t)))) return rc;
+    if ((rc = nfcs_egress_plan_device(ctx_, eg, static_cast<uint8_t*>(d_arena_), off ? off : 16,
+                                      static_cast<nfcs_desc*>(d_desc_), m, nullptr, nullptr,
+                                      static_cast<uint32_t*>(din.p), static_cast<uint32_t*>(dport.p),
+                                      static_cast<uint32_t*>(dops.p), static_cast<uint8_t*>(d_status_), nullptr)))
+        return rc;
+    if ((rc = nfcs_memcpy_d2h(ctx_, ops, dops.p, n * sizeof(uint32_t)))) return rc;
+    return nfcs_memcpy_d2h(ctx_, queue, d_status_, n);
+}
+
+inline int ChecksumEngine::egress_enqueue_batch(const nfcs_egress* eg, const uint32_t* port, const uint8_t* queue,
+                                                size_t n, uint32_t* depth, uint8_t* result, uint32_t* order,
+                                                uint32_t* key_start, uint32_t* key_dropped) {
+    uint32_t keys = 0;
+    if (!eg || !key_start || nfcs_egress_keys(eg, nullptr, &keys)) return NFCS_EINVAL;
+    if (n == 0) return NFCS_OK;
+    if (!port || !queue || !order || (keys && !depth) || n > 0xFFFFFFFFu) return NFCS_EINVAL;
+    std::lock_guard<std::mutex> lock(mu_);
+    int rc = NFCS_OK;
+    DevTmp dport(ctx_, n * sizeof(uint32_t), rc);
+    DevTmp dqueue(ctx_, n, rc);
+    DevTmp dres(ctx_, n, rc);
+    DevTmp dorder(ctx_, n * sizeof(uint32_t), rc);
+    DevTmp ddepth(ctx_, (keys + 1u) * sizeof(uint32_t), rc);
+    DevTmp dks(ctx_, (keys + 1u) * sizeof(uint32_t), rc);
+    DevTmp ddrop(ctx_, (keys + 1u) * sizeof(uint32_t), rc);
+    if (rc) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, dport.p, port, n * sizeof(uint32_t)))) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, dqueue.p, queue, n))) return rc;
+    if (keys && (rc = nfcs_memcpy_h2d(ctx_, ddepth.p, depth, keys * sizeof(uint32_t)))) return rc;
+    if ((rc = nfcs_egress_enqueue_device(ctx_, eg, static_cast<uint32_t*>(dport.p), static_cast<uint8_t*>(dqueue.p),
+                                         static_cast<uint32_t>(n), static_cast<uint32_t*>(ddepth.p),
+                                         static_cast<uint8_t*>(dres.p), static_cast<uint32_t*>(dorder.p),
+                                         static_cast<uint32_t*>(dks.p), static_cast<uint32_t*>(ddrop.p), nullptr)))
+        return rc;
+    if ((rc = nfcs_memcpy_d2h(ctx_, key_start, dks.p, (keys + 1u) * sizeof(uint32_t)))) return rc;
+    if (key_start[keys] > n) return NFCS_EHIP;
+    if (key_start[keys] && (rc = nfcs_memcpy_d2h(ctx_, order, dorder.p, key_start[keys] * sizeof(uint32_t)))) return rc;
+    if (keys && (rc = nfcs_memcpy_d2h(ctx_, depth, ddepth.p, keys * sizeof(uint32_t)))) return rc;
+    if (result && (rc = nfcs_memcpy_d2h(ctx_, result, dres.p, n))) return rc;
+    if (key_dropped && keys && (rc = nfcs_memcpy_d2h(ctx_, key_dropped, ddrop.p, keys * sizeof(uint32_t)))) return rc;
+    return NFCS_OK;
+}
+
 // Same interface as netflow::BufferPool (buffer_pool.hpp:57-123: allocate_buffer(payload,
 // headroom), free_buffer(buffer) with the PacketBuffer reference count), except that every
 // buffer up to slot_bytes is a slot of ONE pinned arena (nfcs_host_alloc). update_checksums_batch
@@ -1018,6 +1106,56 @@ inline int make_fdb_from(const FdbT& fdb, const VlanT& vlans, LinkUp&& link_up, 
     if (rc && f) nfcs_fdb_destroy(f);
     else *out = f;
     return rc;
+}
+
+// Committed egress ports from the switch's VLAN and QoS state, by member name: vlans.get_port_config(port)
+// yields an optional (operator bool, operator->) of a config with type (an enum or integer with ACCESS 0,
+// TRUNK 1, HYBRID 2), native_vlan and tag_native (VlanManager::PortConfig); qos.get_port_qos_config(port)
+// yields an optional of a config with num_queues and max_queue_depth (QosConfig, as configure_port_qos
+// stored it). Ports 0 .. num_ports - 1 are set (num_ports at most NFCS_L2_MAX_PORTS). *out: the object
+// (nfcs_egress_destroy it; upload it with ChecksumEngine::upload_egress before egress_plan_batch), or
+// nullptr on error.
+template <class VlanT, class QosT>
+inline int make_egress_from(const VlanT& vlans, const QosT& qos, uint32_t num_ports, nfcs_egress** out) {
+    if (!out) return NFCS_EINVAL;
+    *out = nullptr;
+    nfcs_egress* g = nullptr;
+    int rc = nfcs_egress_create(&g);
+    for (uint32_t p = 0; !rc && p < num_ports; ++p) {
+        nfcs_egress_port port{};
+        port.port_id = p;
+        const auto cfg = vlans.get_port_config(p);
+        if (cfg) {
+            port.has_vlan_config = 1;
+            port.type = static_cast<uint8_t>(static_cast<int>(cfg->type));
+            port.tag_native = cfg->tag_native ? 1 : 0;
+            port.native_vlan = cfg->native_vlan;
+        }
+        const auto qc = qos.get_port_qos_config(p);
+        if (qc) {
+            port.has_qos = 1;
+            port.num_queues = static_cast<uint8_t>(qc->num_queues);
+            port.max_queue_depth = static_cast<uint32_t>(qc->max_queue_depth);
+        }
+        rc = nfcs_egress_set_port(g, &port);
+    }
+    if (!rc) rc = nfcs_egress_commit(g);
+    if (rc && g) nfcs_egress_destroy(g);
+    else *out = g;
+    return rc;
+}
+
+inline int egress_plan_batch(Packet* const* pkts, size_t n, const nfcs_egress* eg, const uint32_t* egress_port,
+                             uint32_t* ops, uint8_t* queue) {
+    return detail::on_default_engine(
+        [&](ChecksumEngine& e) { return e.egress_plan_batch(pkts, n, eg, egress_port, ops, queue); });
+}
+inline int egress_enqueue_batch(const nfcs_egress* eg, const uint32_t* port, const uint8_t* queue, size_t n,
+                                uint32_t* depth, uint8_t* result, uint32_t* order, uint32_t* key_start,
+                                uint32_t* key_dropped = nullptr) {
+    return detail::on_default_engine([&](ChecksumEngine& e) {
+        return e.egress_enqueue_batch(eg, port, queue, n, depth, result, order, key_start, key_dropped);
+    });
 }
 
 inline int l2_lookup_batch(Packet* const* pkts, size_t n, const nfcs_fdb* fdb, uint32_t ingress_port,

@@ -650,6 +650,136 @@ NFCS_API int nfcs_vlan_device(nfcs_ctx* ctx, uint8_t* d_arena, uint64_t arena_by
                               uint32_t op_all, const uint32_t* d_caps, uint32_t cap_all,
                               uint8_t* d_status, void* stream);
 
+/* ---- Egress stage: VLAN egress plan, QoS classify, enqueue ------------------------------------ */
+
+/* Switch::process_egress_pipeline(pkt, egress_port) (switch.hpp:113-139) for a burst of device-resident
+ * frames: VlanManager::process_egress (vlan_manager.cpp:128-182) decides per egress port whether the tag
+ * is popped, QosManager::classify_packet_to_queue (qos_manager.cpp:78-109) names the queue from the PCP of
+ * the frame as it is after that edit, and QosManager::enqueue_packet (111-153) appends the packet to that
+ * port's queue or tail-drops it at max_queue_depth. nfcs_egress_plan_device makes the two decisions per
+ * packet (read-only on the frames), nfcs_vlan_device applies the edit it is handed (d_ops), and
+ * nfcs_egress_enqueue_device gives, per (port, queue), the packet indexes in arrival order with the tail
+ * drops counted: what a TX side consumes. The symbols of this section were added without changing
+ * NFCS_ABI_VERSION (it stays 2): detect them by symbol lookup (dlsym "nfcs_egress_create").
+ * OUT OF SCOPE:
+ *  - replicating flooded packets: NFCS_L2_FLOOD packets have no port and read NFCS_EQ_SKIP;
+ *  - per-port egress ACLs over a mixed burst: nfcs_acl_eval_device takes one rule list per call. A caller
+ *    with one egress list may still pass d_port as that call's d_nh to mask denied packets; that masking
+ *    also drops REDIRECT, which the reference's egress path treats as PERMIT;
+ *  - scheduling and dequeue (strict priority, WRR, DRR, token buckets): the TX side's, which subtracts
+ *    what it dequeues from d_depth;
+ *  - interface TX counters. */
+
+/* classify_packet_to_queue can name at most 8 distinct queues from the 8 PCP values, so a port has at most
+ * this many queues here, and a port's keys are NFCS_QOS_MAX_QUEUES apart. */
+#define NFCS_QOS_MAX_QUEUES 8u
+#define NFCS_QUEUE_NONE 0xFFu
+/* Packets per tile of nfcs_egress_enqueue_device's partition (one wave takes one tile). SPEED ONLY: the
+ * result never depends on it. Tests place their sizes around it. */
+#define NFCS_EGRESS_TILE_PKTS 1024u
+
+typedef struct nfcs_egress_port {
+    uint32_t port_id;         /* < NFCS_L2_MAX_PORTS (1024), else NFCS_EINVAL                            */
+    uint8_t has_vlan_config;  /* VlanManager::get_port_config(port).has_value()                          */
+    uint8_t type;             /* 0 ACCESS, 1 TRUNK, 2 HYBRID; above 2: NFCS_EINVAL                       */
+    uint8_t tag_native;       /* PortConfig::tag_native                                                  */
+    uint8_t has_qos;          /* QosManager::get_port_qos_config(port).has_value()                       */
+    uint16_t native_vlan;     /* above 4095: NFCS_EINVAL                                                 */
+    uint8_t num_queues;       /* 0 becomes 1 (validate_and_prepare); above NFCS_QOS_MAX_QUEUES: NFCS_EINVAL */
+    uint8_t pad;
+    uint32_t max_queue_depth; /* 0 becomes 1 (validate_and_prepare)                                      */
+} nfcs_egress_port;
+#ifdef __cplusplus
+static_assert(sizeof(nfcs_egress_port) == 16, "nfcs_egress_port is a 16-byte record");
+#endif
+
+/* The egress ports. One nfcs_egress_set_port per port (the same id again replaces it); a port never set,
+ * whatever its id, is the reference's default: no VLAN config and no QoS config. nfcs_egress_clear_ports
+ * forgets every port. nfcs_egress_commit compiles one 16-byte record per port up to the highest id set
+ * (`ports`); a (port, queue) pair is the key port * NFCS_QOS_MAX_QUEUES + queue, there are
+ * keys = ports * NFCS_QOS_MAX_QUEUES of them, and the keys of queues a port does not have stay empty.
+ * Setters, commit and upload behave exactly as in nfcs_fdb: a setter (set_port, clear_ports) invalidates an
+ * earlier commit, so the host functions return NFCS_EINVAL until the next nfcs_egress_commit; it does NOT
+ * invalidate an earlier upload. The object must be destroyed before the ctx. */
+typedef struct nfcs_egress nfcs_egress;
+NFCS_API int nfcs_egress_create(nfcs_egress** out);
+NFCS_API int nfcs_egress_destroy(nfcs_egress* eg); /* also frees what nfcs_egress_upload allocated */
+NFCS_API int nfcs_egress_set_port(nfcs_egress* eg, const nfcs_egress_port* port);
+NFCS_API int nfcs_egress_clear_ports(nfcs_egress* eg);
+NFCS_API int nfcs_egress_commit(nfcs_egress* eg);
+/* Copies the committed records to ctx's device (synchronous; replaces an earlier upload, which must no
+ * longer be in use). NFCS_EINVAL before nfcs_egress_commit. */
+NFCS_API int nfcs_egress_upload(nfcs_ctx* ctx, nfcs_egress* eg);
+/* The committed key space: *ports and *keys (each may be NULL). */
+NFCS_API int nfcs_egress_keys(const nfcs_egress* eg, uint32_t* ports, uint32_t* keys);
+
+/* The decision for one frame leaving through `port`, on the CPU, from the same records the kernel reads:
+ * *op = NFCS_VLAN_POP or NFCS_VLAN_NOP, *queue = the queue (each may be NULL). port == NFCS_IF_NONE gives
+ * NFCS_VLAN_NOP and NFCS_QUEUE_NONE. frame may be NULL when len is 0; only bytes 12..19 are read. */
+NFCS_API int nfcs_egress_plan_host(const nfcs_egress* eg, uint32_t port, const uint8_t* frame, uint32_t len,
+                                   uint32_t* op, uint32_t* queue);
+
+/* The decision per packet over device-resident frames: one kernel, read-only on the frames (bytes 12..19
+ * of each), asynchronous on the stream.
+ *   egress port  d_l3_port[i] when that array is given and its entry is not NFCS_IF_NONE and, when
+ *                d_fwd_status is given as well, d_fwd_status[i] & NFCS_ST_FLAG_FWD (a packet the ACL
+ *                masked, or whose TTL expired, has no egress port); otherwise d_l2_port[i] when given;
+ *                otherwise NFCS_IF_NONE. Both port arrays NULL, or d_fwd_status without d_l3_port:
+ *                NFCS_EINVAL. A packet without a port, or whose descriptor reaches outside the arena (the
+ *                frame is not read), gets NFCS_IF_NONE, NFCS_VLAN_NOP and NFCS_QUEUE_NONE.
+ *   the edit     process_egress: with tagged = len >= 18 and bytes 12-13 = 0x8100 (when vlan_id() has a
+ *                value, and what lets pop_vlan succeed, packet.hpp:604-617, 694-720), POP when the port has
+ *                a VLAN config, the frame is tagged, (TCI & 0x0FFF) == native_vlan, and the port is ACCESS,
+ *                or TRUNK / HYBRID with tag_native clear. NOP otherwise.
+ *   the queue    classify_packet_to_queue on the frame as it will be after that edit. The PCP is that of
+ *                the tag then at byte 14: after a pop the inner tag of a double-tagged frame (old bytes
+ *                16-17 = 0x8100 and len - 4 >= 18, PCP from old byte 18), otherwise the frame's own tag
+ *                when tagged and not popped, otherwise none. With a QoS config and a PCP: num_queues == 4
+ *                maps PCP 6-7 / 4-5 / 2-3 / 0-1 to queue 0 / 1 / 2 / 3, any other count gives
+ *                ((7 - pcp) * num_queues) / 8 in integers (the reference's division by 8.0, truncated),
+ *                clamped to num_queues - 1. With a QoS config and no PCP: num_queues - 1. Without a QoS
+ *                config: 0, as the reference returns.
+ * d_port (n u32), d_ops (n u32, for nfcs_vlan_device) and d_queue (n bytes) are all required.
+ * n == 0 returns NFCS_OK without a launch. eg must be uploaded to ctx (else NFCS_EINVAL). */
+NFCS_API int nfcs_egress_plan_device(nfcs_ctx* ctx, const nfcs_egress* eg, const uint8_t* d_arena,
+                                     uint64_t arena_bytes, const nfcs_desc* d_desc, uint32_t n,
+                                     const uint32_t* d_l3_port, const uint8_t* d_fwd_status,
+                                     const uint32_t* d_l2_port, uint32_t* d_port, uint32_t* d_ops,
+                                     uint8_t* d_queue, void* stream);
+
+/* What enqueue_packet does with a packet (d_result). */
+enum {
+    NFCS_EQ_ENQUEUED = 0,
+    NFCS_EQ_SKIP = 1,           /* d_port[i] == NFCS_IF_NONE                                       */
+    NFCS_EQ_DROP_NO_CONFIG = 2, /* the port has no QoS config (or was never set)                   */
+    NFCS_EQ_DROP_FULL = 3,      /* the queue was at max_queue_depth: tail drop                     */
+    NFCS_EQ_BAD_QUEUE = 4       /* d_queue[i] >= the port's num_queues: not counted                */
+};
+
+/* enqueue_packet for the burst, frame-free: the packets of one key (port * NFCS_QOS_MAX_QUEUES + queue)
+ * are taken in burst order, the first max(0, max_queue_depth - depth) of them are enqueued (the reference
+ * tests size() >= max_queue_depth, so a depth already above the cap leaves no room), the rest are
+ * NFCS_EQ_DROP_FULL, and d_depth[k] grows by the number enqueued, so successive bursts chain on the device.
+ *   d_depth        keys u32, IN/OUT: each queue's depth before / after the burst
+ *   d_result       optional (NULL) n bytes NFCS_EQ_*
+ *   d_order        n u32: the indexes of the ENQUEUED packets grouped by key ascending, arrival order
+ *                  within a key (the queue's FIFO order; the partition is stable and deterministic, no
+ *                  position is handed out by an atomic). Entries past d_key_start[keys] are left as they were.
+ *   d_key_start    keys + 1 u32: key k's packets are d_order[d_key_start[k] .. d_key_start[k+1])
+ *   d_key_dropped  optional (NULL) keys u32: tail drops per key in this burst
+ * n == 0 returns NFCS_OK without a launch (nothing is written). Scratch (a histogram per tile of
+ * NFCS_EGRESS_TILE_PKTS packets) belongs to the context, grows on demand and is freed by nfcs_ctx_destroy;
+ * a failed allocation returns NFCS_ENOMEM and leaves the context usable. With no port set (keys == 0)
+ * every packet with a port reads NFCS_EQ_DROP_NO_CONFIG and d_key_start[0] = 0. */
+NFCS_API int nfcs_egress_enqueue_device(nfcs_ctx* ctx, const nfcs_egress* eg, const uint32_t* d_port,
+                                        const uint8_t* d_queue, uint32_t n, uint32_t* d_depth,
+                                        uint8_t* d_result, uint32_t* d_order, uint32_t* d_key_start,
+                                        uint32_t* d_key_dropped, void* stream);
+/* The same sequential walk on the CPU (host arrays, same meanings; result and key_dropped may be NULL). */
+NFCS_API int nfcs_egress_enqueue_host(const nfcs_egress* eg, const uint32_t* port, const uint8_t* queue,
+                                      uint32_t n, uint32_t* depth, uint8_t* result, uint32_t* order,
+                                      uint32_t* key_start, uint32_t* key_dropped);
+
 /* ---- flow-key extract + hash -------------------------------------------- */
 
 /* PacketClassifier::FlowKey + hash_flow (packet_classifier.hpp:15-56, packet_classifier.cpp:12-108)

@@ -73,6 +73,16 @@ L2_PORT_DTYPE = np.dtype([("port_id", "<u4"), ("link_up", "u1"), ("stp_forwardin
                           ("type", "u1"), ("native_vlan", "<u2"), ("pad", "<u2")])
 assert FDB_ENTRY_DTYPE.itemsize == 16 and L2_PORT_DTYPE.itemsize == 12
 
+# the egress stage (include/nfcs.h nfcs_egress_*, NFCS_EQ_*)
+QOS_MAX_QUEUES = 8      # classify_packet_to_queue names at most 8 queues from 8 PCP values
+QUEUE_NONE = 0xFF
+EGRESS_TILE_PKTS = 1024  # NFCS_EGRESS_TILE_PKTS: the enqueue's tile, speed only
+EQ_ENQUEUED, EQ_SKIP, EQ_DROP_NO_CONFIG, EQ_DROP_FULL, EQ_BAD_QUEUE = range(5)
+EGRESS_PORT_DTYPE = np.dtype([("port_id", "<u4"), ("has_vlan_config", "u1"), ("type", "u1"), ("tag_native", "u1"),
+                              ("has_qos", "u1"), ("native_vlan", "<u2"), ("num_queues", "u1"), ("pad", "u1"),
+                              ("max_queue_depth", "<u4")])
+assert EGRESS_PORT_DTYPE.itemsize == 16
+
 NEXTHOP_DTYPE = np.dtype([("dst_mac", "u1", (6,)), ("src_mac", "u1", (6,))])
 FLOW_KEY_DTYPE = np.dtype([("hash", "<u4"), ("vlan_id", "<u2"), ("ethertype", "<u2"),
                            ("src_mac", "u1", (6,)), ("dst_mac", "u1", (6,)), ("protocol", "u1"),
@@ -192,6 +202,17 @@ def _declare(L):
         "nfcs_fdb_flood_ports_host": ([_vp, _u32, _u32, _u32, _vp, _u32, ctypes.POINTER(_u32)], ctypes.c_int),
         "nfcs_l2_lookup_device": ([_vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp],
                                   ctypes.c_int),
+        "nfcs_egress_create": ([ctypes.POINTER(_vp)], ctypes.c_int),
+        "nfcs_egress_destroy": ([_vp], ctypes.c_int),
+        "nfcs_egress_set_port": ([_vp, _vp], ctypes.c_int),
+        "nfcs_egress_clear_ports": ([_vp], ctypes.c_int),
+        "nfcs_egress_commit": ([_vp], ctypes.c_int),
+        "nfcs_egress_upload": ([_vp, _vp], ctypes.c_int),
+        "nfcs_egress_keys": ([_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)], ctypes.c_int),
+        "nfcs_egress_plan_host": ([_vp, _u32, _vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32)], ctypes.c_int),
+        "nfcs_egress_enqueue_host": ([_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+        "nfcs_egress_plan_device": ([_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+        "nfcs_egress_enqueue_device": ([_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         # a measurement build of an earlier round (NFCS_LIB, A/B runs) may lack a later entry point;
@@ -469,6 +490,96 @@ class Fdb:
             pass
 
 
+class Egress:
+    """The egress ports behind Engine.egress_plan_device / egress_enqueue_device (nfcs_egress): one
+    EGRESS_PORT_DTYPE record per port, holding what VlanManager::process_egress and QosManager::enqueue_packet
+    read of it. A port never set has no VLAN config and no QoS config. The (port, queue) pair is the key
+    port * QOS_MAX_QUEUES + queue."""
+
+    def __init__(self):
+        p = _vp()
+        _check(lib().nfcs_egress_create(ctypes.byref(p)), "nfcs_egress_create")
+        self.ptr = p.value
+
+    def set_port(self, port_id: int, has_vlan_config=True, type=L2_ACCESS, tag_native=False, native_vlan: int = 1,
+                 has_qos=True, num_queues: int = 4, max_queue_depth: int = 1000):
+        """One port (nfcs_egress_port); the same id again replaces it. num_queues 0 and max_queue_depth 0 are
+        each read as 1, as QosConfig::validate_and_prepare does."""
+        rec = np.zeros(1, dtype=EGRESS_PORT_DTYPE)
+        for name, v in (("port_id", port_id), ("type", type), ("native_vlan", native_vlan),
+                        ("num_queues", num_queues), ("max_queue_depth", max_queue_depth)):
+            if not 0 <= int(v) <= np.iinfo(EGRESS_PORT_DTYPE[name]).max:
+                raise NfcsError(f"nfcs_egress_set_port: {name} = {v} does not fit its field")
+            rec[name] = int(v)
+        rec["has_vlan_config"], rec["tag_native"], rec["has_qos"] = bool(has_vlan_config), bool(tag_native), bool(has_qos)
+        _check(lib().nfcs_egress_set_port(self.ptr, rec.ctypes.data), "nfcs_egress_set_port")
+        return self
+
+    def clear_ports(self):
+        _check(lib().nfcs_egress_clear_ports(self.ptr), "nfcs_egress_clear_ports")
+        return self
+
+    def commit(self):
+        _check(lib().nfcs_egress_commit(self.ptr), "nfcs_egress_commit")
+        return self
+
+    def upload(self, engine: "Engine"):
+        """Copy the committed records to the engine's device; close the Egress before the engine."""
+        _check(lib().nfcs_egress_upload(engine.ctx, self.ptr), "nfcs_egress_upload")
+        return self
+
+    def keys(self) -> tuple[int, int]:
+        """(ports, keys) of the committed table: keys = ports * QOS_MAX_QUEUES."""
+        a, b = _u32(), _u32()
+        _check(lib().nfcs_egress_keys(self.ptr, ctypes.byref(a), ctypes.byref(b)), "nfcs_egress_keys")
+        return int(a.value), int(b.value)
+
+    def plan_host(self, port: int, frame: bytes) -> tuple[int, int]:
+        """(VLAN_POP or VLAN_NOP, queue) for one frame leaving through `port`, on the CPU, from the records
+        the kernel reads; (VLAN_NOP, QUEUE_NONE) for IF_NONE."""
+        op, q = _u32(), _u32()
+        frame = bytes(frame)
+        _check(lib().nfcs_egress_plan_host(self.ptr, int(port), frame if frame else None, len(frame), ctypes.byref(op),
+                                           ctypes.byref(q)), "nfcs_egress_plan_host")
+        return int(op.value), int(q.value)
+
+    def enqueue_host(self, port, queue, depth) -> dict:
+        """enqueue_packet over a burst in order, on the CPU: port (n u32) and queue (n bytes) per packet,
+        depth (keys u32) each queue's depth before. Returns depth (after), result (n bytes EQ_*), order (the
+        enqueued packets' indexes grouped by key, arrival order within), key_start (keys + 1) and
+        key_dropped (keys)."""
+        port = np.ascontiguousarray(port, dtype=np.uint32)
+        queue = np.ascontiguousarray(queue, dtype=np.uint8)
+        n, keys = len(port), self.keys()[1]
+        if len(queue) != n or len(depth) != keys:
+            raise NfcsError("enqueue_host: port and queue need n entries each, depth one per key")
+        depth = np.array(depth, dtype=np.uint32)
+        result, order = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        key_start, key_dropped = np.zeros(keys + 1, np.uint32), np.zeros(keys, np.uint32)
+        dp = lambda a: a.ctypes.data if len(a) else None
+        _check(lib().nfcs_egress_enqueue_host(self.ptr, dp(port), dp(queue), n, dp(depth), dp(result), dp(order),
+                                              key_start.ctypes.data, dp(key_dropped)), "nfcs_egress_enqueue_host")
+        return {"depth": depth, "result": result, "order": order[:int(key_start[keys])], "key_start": key_start,
+                "key_dropped": key_dropped}
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            lib().nfcs_egress_destroy(self.ptr)
+            self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceBuffer:
     """A raw device allocation owned by an Engine (no torch types involved)."""
 
@@ -661,6 +772,28 @@ class Engine:
         _check(lib().nfcs_l2_lookup_device(self.ctx, fdb.ptr, int(ingress_port), ptr(arena), arena_bytes, ptr(desc), n,
                                            ptr(rt_verdict), ptr(egress_port), ptr(verdict), ptr(vlan), ptr(learn),
                                            stream), "nfcs_l2_lookup_device")
+
+    def egress_plan_device(self, egress: "Egress", arena, arena_bytes: int, desc, n: int, port, ops, queue,
+                           l3_port=None, fwd_status=None, l2_port=None, stream=None):
+        """process_egress + classify_packet_to_queue per frame on device frames, read-only: port (n u32: the
+        packet's egress port or IF_NONE), ops (n u32 VLAN_POP / VLAN_NOP, ready for vlan_device) and queue (n
+        bytes, QUEUE_NONE without a port). The port is l3_port[i] (route_lookup_device's egress_if; with
+        fwd_status, l3_forward_device's status, only where ST_FLAG_FWD is set), else l2_port[i]
+        (l2_lookup_device's egress_port)."""
+        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
+        _check(lib().nfcs_egress_plan_device(self.ctx, egress.ptr, ptr(arena), arena_bytes, ptr(desc), n, ptr(l3_port),
+                                             ptr(fwd_status), ptr(l2_port), ptr(port), ptr(ops), ptr(queue), stream),
+               "nfcs_egress_plan_device")
+
+    def egress_enqueue_device(self, egress: "Egress", port, queue, n: int, depth, order, key_start, result=None,
+                              key_dropped=None, stream=None):
+        """enqueue_packet for the burst: depth (keys u32, in/out), order (n u32: the enqueued packets' indexes
+        grouped by key, arrival order within), key_start (keys + 1 u32); result (n bytes EQ_*) and key_dropped
+        (keys u32) optional."""
+        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
+        _check(lib().nfcs_egress_enqueue_device(self.ctx, egress.ptr, ptr(port), ptr(queue), n, ptr(depth), ptr(result),
+                                                ptr(order), ptr(key_start), ptr(key_dropped), stream),
+               "nfcs_egress_enqueue_device")
 
     def vlan_device(self, arena, arena_bytes: int, desc, n: int, ops=None, op_all: int = 0,
                     caps=None, cap_all: int = 0, status=None, stream=None):

@@ -166,6 +166,14 @@ struct nfcs_ctx {
     hipStream_t ws_stream = nullptr;
     bool ws_used = false;
     bool ws_own = false;
+    // nfcs_egress_enqueue_device's scratch (tile histograms, totals, rooms), grown on demand; its last
+    // user ran on eq_stream, and eq_ev orders a call on another stream behind it, as ws_ev does for ws
+    uint32_t* eq_ws = nullptr;
+    uint64_t eq_cap = 0;  // words
+    hipEvent_t eq_ev = nullptr;
+    hipStream_t eq_stream = nullptr;
+    bool eq_used = false;
+    bool eq_own = false;
     uint32_t slot_bytes = 0;  // launch-shape hint (nfcs_ctx_set_slot_bytes); 0 = arena_bytes / n
     // the footprint observations (launch_shape): kObsSlots host-mapped 64-bit slots the kernels
     // write ({generation, mean}), one per recently seen burst (descriptor array, n, arena bytes),
@@ -225,6 +233,47 @@ hipError_t release_ws(nfcs_ctx* c, hipStream_t st) {
     c->ws_own = st == c->stream;
     // a caller's stream may be gone by the time another stream comes: its event is recorded now
     return c->ws_own ? hipSuccess : hipEventRecord(c->ws_ev, st);
+}
+
+// The same for the enqueue's scratch (eq_ws): `words` words for a launch on `st`. A failed allocation
+// leaves the context without scratch and otherwise as it was.
+hipError_t wait_eq_user(nfcs_ctx* c, hipStream_t st) {
+    if (c->eq_own) {
+        hipError_t e = hipEventRecord(c->eq_ev, c->stream);
+        if (e != hipSuccess) return e;
+    }
+    return st ? hipStreamWaitEvent(st, c->eq_ev, 0) : hipEventSynchronize(c->eq_ev);
+}
+hipError_t acquire_eq(nfcs_ctx* c, uint64_t words, hipStream_t st) {
+    if (words > c->eq_cap) {
+        if (c->eq_used) {
+            hipError_t e = wait_eq_user(c, nullptr);  // on the host: the buffer is freed next
+            if (e != hipSuccess) return e;
+        }
+        if (c->eq_ws) (void)hipFree(c->eq_ws);
+        c->eq_ws = nullptr;
+        c->eq_cap = 0;
+        c->eq_used = false;
+        const uint64_t cap = words < (1u << 18) ? (1u << 18) : words;
+        if (cap > (uint64_t)SIZE_MAX / sizeof(uint32_t)) return hipErrorOutOfMemory;
+        hipError_t e = hipMalloc(&c->eq_ws, (size_t)cap * sizeof(uint32_t));
+        if (e != hipSuccess) {  // whatever the runtime calls it: the caller sees NFCS_ENOMEM
+            c->eq_ws = nullptr;
+            (void)hipGetLastError();
+            return hipErrorOutOfMemory;
+        }
+        c->eq_cap = cap;
+    } else if (c->eq_used && c->eq_stream != st) {
+        hipError_t e = wait_eq_user(c, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+hipError_t release_eq(nfcs_ctx* c, hipStream_t st) {
+    c->eq_stream = st;
+    c->eq_used = true;
+    c->eq_own = st == c->stream;
+    return c->eq_own ? hipSuccess : hipEventRecord(c->eq_ev, st);
 }
 
 int hip_fail(hipError_t e) {
@@ -851,6 +900,7 @@ NFCS_API int nfcs_ctx_create(int device, nfcs_ctx** out) {
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipMalloc(&c->d_digest, sizeof(uint64_t));
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ws_ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->eq_ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreate(&c->ev0);
     if (e == hipSuccess) e = hipEventCreate(&c->ev1);
     if (e == hipSuccess) e = hipHostMalloc((void**)&c->obs_host, nfcs_ctx::kObsSlots * sizeof(uint64_t), hipHostMallocMapped);
@@ -871,8 +921,11 @@ NFCS_API int nfcs_ctx_destroy(nfcs_ctx* c) {
     DeviceGuard dg_(c->di.device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->ws_used && !c->ws_own && c->ws_ev) (void)hipEventSynchronize(c->ws_ev);  // a caller stream's last write pass
+    if (c->eq_used && !c->eq_own && c->eq_ev) (void)hipEventSynchronize(c->eq_ev);  // a caller stream's last enqueue
     free_host_pipeline(c);
     if (c->d_digest) (void)hipFree(c->d_digest);
+    if (c->eq_ws) (void)hipFree(c->eq_ws);
+    if (c->eq_ev) (void)hipEventDestroy(c->eq_ev);
     if (c->ws) (void)hipFree(c->ws);
     if (c->ws_ev) (void)hipEventDestroy(c->ws_ev);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1398,6 +1451,171 @@ NFCS_API int nfcs_l2_lookup_device(nfcs_ctx* c, const nfcs_fdb* f, uint32_t ingr
     if (((uintptr_t)d_egress_port & 3u) || ((uintptr_t)d_vlan & 1u)) return NFCS_EINVAL;
     NFCS_HIP(nfcs::launch_l2_lookup(c->di, f->dev, ingress_port, d_arena, arena_bytes, d_desc, n, d_rt_verdict,
                                     d_egress_port, d_verdict, d_vlan, d_learn, pick(c, stream)));
+    return NFCS_OK;
+}
+
+// ---- Egress stage (nfcs_egress.h: compile, host plan, host enqueue) and its kernels ----------------
+}  // extern "C"
+
+struct nfcs_egress {
+    nfcs::EgressInputs in;
+    nfcs::EgressTables t;
+    bool committed = false;
+    // nfcs_egress_upload: the records on `device`
+    int device = -1;
+    uint8_t* d_blob = nullptr;
+    nfcs::EgressDev dev;
+    bool uploaded = false;
+};
+
+namespace {
+void egress_drop_upload(nfcs_egress* g) {
+    if (g->d_blob) {
+        DeviceGuard dg_(g->device);
+        if (dg_.err == hipSuccess) (void)hipFree(g->d_blob);
+    }
+    g->d_blob = nullptr;
+    g->dev = nfcs::EgressDev{};
+    g->uploaded = false;
+}
+}  // namespace
+
+extern "C" {
+
+NFCS_API int nfcs_egress_create(nfcs_egress** out) {
+    if (!out) return NFCS_EINVAL;
+    *out = new (std::nothrow) nfcs_egress();
+    return *out ? NFCS_OK : NFCS_ENOMEM;
+}
+
+NFCS_API int nfcs_egress_destroy(nfcs_egress* g) {
+    if (!g) return NFCS_EINVAL;
+    egress_drop_upload(g);
+    delete g;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_egress_set_port(nfcs_egress* g, const nfcs_egress_port* port) {
+    if (!g || !port) return NFCS_EINVAL;
+    if (port->port_id >= NFCS_L2_MAX_PORTS || port->type > 2u || port->native_vlan > 4095u ||
+        port->num_queues > NFCS_QOS_MAX_QUEUES)
+        return NFCS_EINVAL;
+    try {
+        if (g->in.ports.size() <= port->port_id) g->in.ports.resize(port->port_id + 1u);
+        g->in.ports[port->port_id].port = *port;
+        g->in.ports[port->port_id].set = true;
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+    g->committed = false;  // the device copy, if any, stays as it is until the next upload
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_egress_clear_ports(nfcs_egress* g) {
+    if (!g) return NFCS_EINVAL;
+    g->in.ports.clear();
+    g->committed = false;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_egress_commit(nfcs_egress* g) {
+    if (!g) return NFCS_EINVAL;
+    try {
+        nfcs::egress_compile(g->in, g->t);
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+    g->committed = true;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_egress_upload(nfcs_ctx* c, nfcs_egress* g) {
+    if (!c || !g || !g->committed) return NFCS_EINVAL;
+    egress_drop_upload(g);
+    DeviceGuard dg_(c->di.device);
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    const size_t bytes = g->t.recs.size() * sizeof(nfcs::EgressRec);
+    NFCS_HIP(hipMalloc(&g->d_blob, bytes + 16u));
+    g->device = c->di.device;
+    hipError_t e = hipMemset(g->d_blob, 0, bytes + 16u);
+    if (e == hipSuccess && bytes) e = hipMemcpy(g->d_blob, g->t.recs.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        egress_drop_upload(g);
+        return hip_fail(e);
+    }
+    g->dev.recs = (const uint4*)g->d_blob;
+    g->dev.ports = g->t.ports;
+    g->dev.keys = g->t.keys;
+    g->uploaded = true;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_egress_keys(const nfcs_egress* g, uint32_t* ports, uint32_t* keys) {
+    if (!g || !g->committed) return NFCS_EINVAL;
+    if (ports) *ports = g->t.ports;
+    if (keys) *keys = g->t.keys;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_egress_plan_host(const nfcs_egress* g, uint32_t port, const uint8_t* frame, uint32_t len,
+                                   uint32_t* op, uint32_t* queue) {
+    if (!g || !g->committed || (len > 0 && !frame)) return NFCS_EINVAL;
+    nfcs::egress_plan(g->t, port, frame, len, op, queue);
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_egress_enqueue_host(const nfcs_egress* g, const uint32_t* port, const uint8_t* queue, uint32_t n,
+                                      uint32_t* depth, uint8_t* result, uint32_t* order, uint32_t* key_start,
+                                      uint32_t* key_dropped) {
+    if (!g || !g->committed || !key_start || (g->t.keys > 0 && !depth)) return NFCS_EINVAL;
+    if (n > 0 && (!port || !queue || !order)) return NFCS_EINVAL;
+    try {
+        nfcs::egress_enqueue(g->t, port, queue, n, depth, result, order, key_start, key_dropped);
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_egress_plan_device(nfcs_ctx* c, const nfcs_egress* g, const uint8_t* d_arena, uint64_t arena_bytes,
+                                     const nfcs_desc* d_desc, uint32_t n, const uint32_t* d_l3_port,
+                                     const uint8_t* d_fwd_status, const uint32_t* d_l2_port, uint32_t* d_port,
+                                     uint32_t* d_ops, uint8_t* d_queue, void* stream) {
+    if (!c || !g || !g->uploaded || g->device != c->di.device) return NFCS_EINVAL;
+    if ((!d_l3_port && !d_l2_port) || (d_fwd_status && !d_l3_port)) return NFCS_EINVAL;
+    DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    if (n == 0) return NFCS_OK;
+    if (!d_arena || !d_desc || !d_port || !d_ops || !d_queue || ((uintptr_t)d_arena & 15u)) return NFCS_EINVAL;
+    if (((uintptr_t)d_l3_port & 3u) || ((uintptr_t)d_l2_port & 3u) || ((uintptr_t)d_port & 3u) || ((uintptr_t)d_ops & 3u))
+        return NFCS_EINVAL;
+    NFCS_HIP(nfcs::launch_egress_plan(c->di, g->dev, d_arena, arena_bytes, d_desc, n, d_l3_port, d_fwd_status, d_l2_port,
+                                      d_port, d_ops, d_queue, pick(c, stream)));
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_egress_enqueue_device(nfcs_ctx* c, const nfcs_egress* g, const uint32_t* d_port, const uint8_t* d_queue,
+                                        uint32_t n, uint32_t* d_depth, uint8_t* d_result, uint32_t* d_order,
+                                        uint32_t* d_key_start, uint32_t* d_key_dropped, void* stream) {
+    if (!c || !g || !g->uploaded || g->device != c->di.device) return NFCS_EINVAL;
+    DeviceGuard dg_(c->di.device);
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    if (n == 0) return NFCS_OK;
+    if (!d_port || !d_queue || !d_order || !d_key_start || (g->dev.keys > 0 && !d_depth)) return NFCS_EINVAL;
+    if (((uintptr_t)d_port & 3u) || ((uintptr_t)d_depth & 3u) || ((uintptr_t)d_order & 3u) ||
+        ((uintptr_t)d_key_start & 3u) || ((uintptr_t)d_key_dropped & 3u))
+        return NFCS_EINVAL;
+    hipStream_t st = pick(c, stream);
+    const uint64_t words = nfcs::egress_scratch_words(n, g->dev.keys);
+    hipError_t e = acquire_eq(c, words, st);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();  // the context stays usable: only this call's scratch is missing
+        return NFCS_ENOMEM;
+    }
+    NFCS_HIP(e);
+    NFCS_HIP(nfcs::launch_egress_enqueue(c->di, g->dev, d_port, d_queue, n, d_depth, d_result, d_order, d_key_start,
+                                         d_key_dropped, c->eq_ws, st));
+    NFCS_HIP(release_eq(c, st));
     return NFCS_OK;
 }
 

@@ -7,6 +7,7 @@
 
 #include "nfcs.h"
 #include "nfcs_acl.h"
+#include "nfcs_egress.h"
 #include "nfcs_fdb.h"
 #include "nfcs_fib.h"
 
@@ -227,6 +228,30 @@ hipError_t launch_l2_lookup(const DevInfo& di, const FdbDev& fdb, uint32_t ingre
                             uint64_t arena_bytes, const nfcs_desc* desc, uint32_t n, const uint8_t* rt_verdict,
                             uint32_t* egress_port, uint8_t* verdict, uint16_t* vlan, uint8_t* learn,
                             hipStream_t stream);
+
+// The committed egress ports in device memory (nfcs_egress_upload; the records of EgressTables, nfcs_egress.h).
+struct EgressDev {
+    const uint4* recs = nullptr;  // ports 16-byte records {flags, native, queues, max_depth}, 16-byte aligned
+    uint32_t ports = 0, keys = 0;
+};
+
+hipError_t launch_egress_plan(const DevInfo& di, const EgressDev& eg, const uint8_t* arena, uint64_t arena_bytes,
+                              const nfcs_desc* desc, uint32_t n, const uint32_t* l3_port, const uint8_t* fwd_status,
+                              const uint32_t* l2_port, uint32_t* port, uint32_t* ops, uint8_t* queue,
+                              hipStream_t stream);
+
+// The enqueue's partition. Tiles of kEgTile consecutive packets, one wave each.
+constexpr uint32_t kEgTile = NFCS_EGRESS_TILE_PKTS;
+static_assert(kEgTile % 64u == 0 && kEgTile >= 64u, "a tile is whole rounds of one wave");
+// Scratch words for a burst of n packets over `keys` keys: tiles x keys tile histograms (then each
+// tile's start per key), keys totals, keys rooms.
+inline uint64_t egress_scratch_words(uint32_t n, uint32_t keys) {
+    const uint64_t tiles = ((uint64_t)n + kEgTile - 1u) / kEgTile;
+    return tiles * keys + 2ull * keys;
+}
+hipError_t launch_egress_enqueue(const DevInfo& di, const EgressDev& eg, const uint32_t* port, const uint8_t* queue,
+                                 uint32_t n, uint32_t* depth, uint8_t* result, uint32_t* order, uint32_t* key_start,
+                                 uint32_t* key_dropped, uint32_t* scratch, hipStream_t stream);
 
 hipError_t launch_gen_config(const DevInfo& di, int config, uint64_t seed, uint64_t first,
                              uint32_t n, uint8_t* arena, uint64_t arena_bytes,

@@ -2525,6 +2525,289 @@ hipError_t launch_l2_lookup(const DevInfo& di, const FdbDev& fdb, uint32_t ingre
     return hipGetLastError();
 }
 
+// ---- Egress stage: VLAN egress plan, QoS classify, enqueue ---------------------
+// The plan: process_egress and classify_packet_to_queue per packet, l2_lookup_kernel's shape: a wave takes
+// 64 packets, one lane each, with route_lookup_kernel's descriptor load, liveness test and XCD-aware block
+// order. The decision reads frame bytes 12..19, which straddle chunks 0 and 1: the packet's own lane loads
+// them with ONE 8-byte load at byte 12 (4-byte aligned, as every frame starts on a 16-byte boundary;
+// non-temporal: the frames are streamed), or the 4 bytes 12..15 alone when the frame ends inside chunk 0
+// (chunk 1 may then lie outside the arena). Two 16-byte chunk loads, the first form, touched every frame's
+// line in two instructions and took 1.77 times the yardstick's time on C1. The port's
+// 16-byte record is read with the default cache policy (it is the reused data). No LDS, no loop.
+typedef uint32_t u32x2_a4_t __attribute__((ext_vector_type(2), aligned(4)));
+DEV EgressRec eg_rec(const EgressDev& eg, uint32_t port, bool want) {
+    uint4 r = make_uint4(0u, 0u, 0u, 0u);  // a port never set: no VLAN config, no QoS config
+    if (want && port < eg.ports) r = eg.recs[port];
+    return EgressRec{r.x, r.y, r.z, r.w};
+}
+
+__global__ __launch_bounds__(kBlock) void egress_plan_kernel(const nfcs_desc* __restrict__ desc, uint32_t n,
+                                                             uint32_t nblocks, const uint8_t* __restrict__ arena,
+                                                             uint64_t arena_bytes, const EgressDev eg,
+                                                             const uint32_t* __restrict__ l3_port,
+                                                             const uint8_t* __restrict__ fwd_status,
+                                                             const uint32_t* __restrict__ l2_port,
+                                                             uint32_t* __restrict__ port_out,
+                                                             uint32_t* __restrict__ ops_out,
+                                                             uint8_t* __restrict__ queue_out) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t p0 = ((uint64_t)xcd_block_n(nblocks) * kWavesPerBlock + rfl(wave)) * 64u;
+    if (p0 >= n) return;
+    // lane l: descriptor and ports of packet p0 + l (coalesced loads); dead packets read as length 0
+    const uint64_t p = p0 + lane;
+    uint2 dl = make_uint2(0u, 0u);
+    uint32_t port = NFCS_IF_NONE;
+    if (p < n) {
+        dl = ((const uint2*)desc)[p];
+        uint32_t l3 = l3_port ? l3_port[p] : NFCS_IF_NONE;
+        if (fwd_status && !(fwd_status[p] & NFCS_ST_FLAG_FWD)) l3 = NFCS_IF_NONE;  // masked by the ACL, TTL expired
+        port = l3 != NFCS_IF_NONE ? l3 : l2_port ? l2_port[p] : NFCS_IF_NONE;
+    }
+    const uint64_t off = (uint64_t)dl.x * 16u;
+    const bool live = p < n && port != NFCS_IF_NONE && off + (((uint64_t)dl.y + 15u) & ~15ull) <= arena_bytes;
+    const uint32_t len = live ? dl.y : 0u;
+    const EgressRec r = eg_rec(eg, port, live);
+    // bytes 12..15 lie in chunk 0 once the frame has an Ethernet header; chunk 1 lies inside the arena
+    // when len > 16 (the descriptor test covers len rounded up to 16)
+    uint32_t w3 = 0, w4 = 0;
+    if (len > 16u) {
+        const u32x2_a4_t t = __builtin_nontemporal_load((const u32x2_a4_t*)(arena + off + 12u));
+        w3 = t.x;
+        w4 = t.y;
+    } else if (len >= 14u) {
+        w3 = __builtin_nontemporal_load((const uint32_t*)(arena + off + 12u));
+    }
+    uint32_t op, q;
+    egress_plan_rec(r, len, w3, w4, &op, &q);
+    if (p < n) {  // one packet per lane: each store instruction writes consecutive elements
+        port_out[p] = live ? port : NFCS_IF_NONE;
+        ops_out[p] = live ? op : NFCS_VLAN_NOP;
+        queue_out[p] = (uint8_t)(live ? q : NFCS_QUEUE_NONE);
+    }
+}
+
+hipError_t launch_egress_plan(const DevInfo& di, const EgressDev& eg, const uint8_t* arena, uint64_t arena_bytes,
+                              const nfcs_desc* desc, uint32_t n, const uint32_t* l3_port, const uint8_t* fwd_status,
+                              const uint32_t* l2_port, uint32_t* port, uint32_t* ops, uint8_t* queue,
+                              hipStream_t stream) {
+    (void)di;
+    if (n == 0) return hipSuccess;
+    const uint32_t g = (n + 255u) / 256u;
+    hipLaunchKernelGGL(egress_plan_kernel, dim3(g), dim3(kBlock), 0, stream, desc, n, g, arena, arena_bytes, eg, l3_port,
+                       fwd_status, l2_port, port, ops, queue);
+    return hipGetLastError();
+}
+
+// The enqueue: a stable partition of the burst by key = port * NFCS_QOS_MAX_QUEUES + queue, clamped by
+// each queue's room. Four kernels over tiles of kEgTile consecutive packets, one 64-lane workgroup (one
+// wave) per tile, so nothing orders waves inside a tile:
+//   1. egress_hist_kernel: the tile's packets per key, counted in LDS (keys words), to hist[tile][key].
+//   2. egress_scan_tiles_kernel: per key down the tiles: hist[tile][key] becomes the arrival index of the
+//      tile's first packet of that key, total[key] the key's packets. 64 keys x 16 tile segments per
+//      workgroup: a segment sums its tiles, the 16 partial sums meet in LDS, the segment writes its prefix.
+//   3. egress_scan_keys_kernel (one workgroup): room = max(0, max_depth - depth), enqueued = min(total,
+//      room), the exclusive scan of `enqueued` across keys into key_start, depth += enqueued, the drops.
+//   4. egress_scatter_kernel: the tile's running count per key in LDS, starting from hist[tile][key]. Per
+//      round of 64 packets each lane finds the lanes that hold its key (one ballot per key bit: kbits
+//      ballots, a count fixed by the table), its rank among them is a population count of the lower lanes,
+//      every lane reads the key's count and the highest lane of each key then adds the key's lanes to it.
+//      A packet's arrival index is count + rank; it is enqueued while that is below the key's room, at
+//      order[key_start[key] + index]. No position comes from an atomic and no loop ends on data.
+// Packets that are not counted (NFCS_EQ_SKIP / DROP_NO_CONFIG / BAD_QUEUE) take no part in a key.
+constexpr uint32_t kEgRounds = kEgTile / 64u;  // rounds of 64 packets per tile
+DEV uint32_t eg_class_at(const EgressDev& eg, const uint32_t* __restrict__ port, const uint8_t* __restrict__ queue,
+                         uint64_t i, uint32_t n, uint32_t* key) {
+    if (i >= n) return NFCS_EQ_SKIP;
+    const uint32_t pt = port[i], q = queue[i];
+    const bool has = pt < eg.ports;  // NFCS_IF_NONE is never below ports (at most NFCS_L2_MAX_PORTS)
+    return egress_class(pt, q, has, eg_rec(eg, pt, has), key);
+}
+
+__global__ __launch_bounds__(64) void egress_hist_kernel(const uint32_t* __restrict__ port,
+                                                         const uint8_t* __restrict__ queue, uint32_t n,
+                                                         const EgressDev eg, uint32_t* __restrict__ hist) {
+    extern __shared__ uint32_t eg_cnt[];  // eg.keys words
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t k = lane; k < eg.keys; k += 64u) eg_cnt[k] = 0u;
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * kEgTile;
+#pragma unroll 4
+    for (uint32_t r = 0; r < kEgRounds; ++r) {
+        uint32_t key = 0;
+        if (eg_class_at(eg, port, queue, base + r * 64u + lane, n, &key) == NFCS_EQ_ENQUEUED)
+            atomicAdd(&eg_cnt[key], 1u);  // key < eg.keys: port < ports, queue < queues <= 8. A count, not a position.
+    }
+    __syncthreads();
+    uint32_t* row = hist + (size_t)blockIdx.x * eg.keys;
+    for (uint32_t k = lane; k < eg.keys; k += 64u) row[k] = eg_cnt[k];
+}
+
+constexpr uint32_t kEgSegs = 16;  // tile segments per workgroup of egress_scan_tiles_kernel
+__global__ __launch_bounds__(64 * kEgSegs) void egress_scan_tiles_kernel(uint32_t* __restrict__ hist, uint32_t tiles,
+                                                                         uint32_t keys, uint32_t* __restrict__ total) {
+    __shared__ uint32_t part[kEgSegs][64];
+    const uint32_t lane = threadIdx.x & 63u, seg = threadIdx.x >> 6;
+    const uint32_t key = blockIdx.x * 64u + lane;
+    const uint32_t per = (tiles + kEgSegs - 1u) / kEgSegs;
+    const uint32_t t0 = min(seg * per, tiles), t1 = min(t0 + per, tiles);
+    const bool mine = key < keys;
+    uint32_t sum = 0;
+    if (mine) {
+#pragma unroll 8
+        for (uint32_t t = t0; t < t1; ++t) sum += hist[(size_t)t * keys + key];
+    }
+    part[seg][lane] = sum;
+    __syncthreads();
+    uint32_t run = 0, all = 0;
+#pragma unroll
+    for (uint32_t s = 0; s < kEgSegs; ++s) {
+        const uint32_t v = part[s][lane];
+        run += s < seg ? v : 0u;
+        all += v;
+    }
+    if (!mine) return;
+    // eight tiles' counts are loaded before the first prefix is stored: a store to hist keeps the loads behind
+    // it from being issued early, and one load per store made this kernel 13-15 us on 1,024 tiles (§16)
+    for (uint32_t t = t0; t < t1; t += 8u) {
+        uint32_t v[8];
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; ++j) v[j] = hist[(size_t)min(t + j, t1 - 1u) * keys + key];
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; ++j) {
+            if (t + j < t1) {
+                hist[(size_t)(t + j) * keys + key] = run;
+                run += v[j];
+            }
+        }
+    }
+    if (seg == 0) total[key] = all;
+}
+
+constexpr uint32_t kEgScanThreads = 1024;
+constexpr uint32_t kEgKeysPerThread = NFCS_L2_MAX_PORTS * NFCS_QOS_MAX_QUEUES / kEgScanThreads;  // 8: every key has a thread
+static_assert(kEgKeysPerThread * kEgScanThreads == NFCS_L2_MAX_PORTS * NFCS_QOS_MAX_QUEUES, "one workgroup scans every key");
+__global__ __launch_bounds__(kEgScanThreads) void egress_scan_keys_kernel(const EgressDev eg,
+                                                                          const uint32_t* __restrict__ total,
+                                                                          uint32_t* __restrict__ depth,
+                                                                          uint32_t* __restrict__ room,
+                                                                          uint32_t* __restrict__ key_start,
+                                                                          uint32_t* __restrict__ key_dropped) {
+    __shared__ uint32_t scan[kEgScanThreads];
+    const uint32_t tid = threadIdx.x;
+    // kEgKeysPerThread consecutive keys per thread, read once into registers (clamped loads, so that they are
+    // all in flight together) and used again after the scan
+    const uint32_t k0 = tid * kEgKeysPerThread, last = eg.keys ? eg.keys - 1u : 0u;
+    uint32_t rm[kEgKeysPerThread], tot[kEgKeysPerThread], dep[kEgKeysPerThread];
+    uint32_t sum = 0;
+    if (eg.keys) {  // with no key at all depth and total may be null: nothing is loaded
+#pragma unroll
+        for (uint32_t j = 0; j < kEgKeysPerThread; ++j) {
+            const uint32_t k = min(k0 + j, last);
+            const bool mine = k0 + j < eg.keys;
+            const uint32_t cap = eg.recs[k / NFCS_QOS_MAX_QUEUES].w;
+            dep[j] = depth[k];
+            tot[j] = total[k];
+            if (!mine) tot[j] = 0u;
+            rm[j] = cap > dep[j] ? cap - dep[j] : 0u;  // size() >= max_queue_depth: no room, no underflow
+            sum += min(tot[j], rm[j]);
+        }
+    }
+    scan[tid] = sum;
+    __syncthreads();
+    for (uint32_t s = 1; s < kEgScanThreads; s *= 2u) {  // inclusive scan over the threads' sums
+        const uint32_t v = tid >= s ? scan[tid - s] : 0u;
+        __syncthreads();
+        scan[tid] += v;
+        __syncthreads();
+    }
+    uint32_t run = scan[tid] - sum;
+#pragma unroll
+    for (uint32_t j = 0; j < kEgKeysPerThread; ++j) {
+        const uint32_t k = k0 + j;
+        if (k < eg.keys) {
+            const uint32_t e = min(tot[j], rm[j]);
+            key_start[k] = run;
+            run += e;
+            depth[k] = dep[j] + e;
+            room[k] = rm[j];
+            if (key_dropped) key_dropped[k] = tot[j] - e;
+        }
+    }
+    if (tid == kEgScanThreads - 1u) key_start[eg.keys] = scan[tid];
+}
+
+__global__ __launch_bounds__(64) void egress_scatter_kernel(const uint32_t* __restrict__ port,
+                                                            const uint8_t* __restrict__ queue, uint32_t n,
+                                                            const EgressDev eg, uint32_t kbits,
+                                                            const uint32_t* __restrict__ hist,
+                                                            const uint32_t* __restrict__ room,
+                                                            const uint32_t* __restrict__ key_start,
+                                                            uint8_t* __restrict__ result,
+                                                            uint32_t* __restrict__ order) {
+    extern __shared__ uint32_t eg_cnt[];  // eg.keys words: the arrival index of the key's next packet
+    const uint32_t lane = threadIdx.x;
+    const uint32_t* row = hist + (size_t)blockIdx.x * eg.keys;
+    for (uint32_t k = lane; k < eg.keys; k += 64u) eg_cnt[k] = row[k];
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * kEgTile, below = (1ull << lane) - 1ull;
+    // One pass over the tile's rounds. Splitting it into three unrolled passes (classes and keys; arrival
+    // indexes; rooms, starts and stores) with unconditional clamped loads, so that each pass's loads are in
+    // flight together, measured 6-15% slower (102 VGPRs).
+    for (uint32_t r = 0; r < kEgRounds; ++r) {
+        const uint64_t i = base + r * 64u + lane;
+        uint32_t key = 0;
+        uint32_t c = eg_class_at(eg, port, queue, i, n, &key);
+        const bool keyed = c == NFCS_EQ_ENQUEUED;
+        // the lanes that hold this lane's key
+        uint64_t peers = __builtin_amdgcn_ballot_w64(keyed);
+        for (uint32_t b = 0; b < kbits; ++b) {
+            const bool bit = (key >> b) & 1u;
+            const uint64_t has = __builtin_amdgcn_ballot_w64(keyed && bit);
+            peers &= bit ? has : ~has;
+        }
+        const uint32_t rank = (uint32_t)__popcll(peers & below), cnt = (uint32_t)__popcll(peers);
+        uint32_t at = 0;
+        if (keyed) at = eg_cnt[key];
+        __syncthreads();  // one wave: every lane has read before the keys' highest lanes write
+        if (keyed && rank + 1u == cnt) eg_cnt[key] = at + cnt;
+        __syncthreads();
+        if (keyed) {
+            const uint32_t a = at + rank;
+            if (a < room[key]) {
+                const uint32_t pos = key_start[key] + a;
+                if (pos < n) order[pos] = (uint32_t)i;  // always true: enqueued packets number at most n
+            } else {
+                c = NFCS_EQ_DROP_FULL;
+            }
+        }
+        if (result && i < n) result[i] = (uint8_t)c;
+    }
+}
+
+hipError_t launch_egress_enqueue(const DevInfo& di, const EgressDev& eg, const uint32_t* port, const uint8_t* queue,
+                                 uint32_t n, uint32_t* depth, uint8_t* result, uint32_t* order, uint32_t* key_start,
+                                 uint32_t* key_dropped, uint32_t* scratch, hipStream_t stream) {
+    (void)di;
+    if (n == 0) return hipSuccess;
+    const uint32_t tiles = (uint32_t)(((uint64_t)n + kEgTile - 1u) / kEgTile), keys = eg.keys;
+    uint32_t* hist = scratch;
+    uint32_t* total = scratch + (size_t)tiles * keys;
+    uint32_t* room = total + keys;
+    const size_t lds = (size_t)keys * sizeof(uint32_t);  // at most 1024 ports x 8 queues x 4 bytes = 32 KiB
+    uint32_t kbits = 0;
+    while ((1u << kbits) < keys) ++kbits;
+    if (keys) {
+        hipLaunchKernelGGL(egress_hist_kernel, dim3(tiles), dim3(64), lds, stream, port, queue, n, eg, hist);
+        hipLaunchKernelGGL(egress_scan_tiles_kernel, dim3((keys + 63u) / 64u), dim3(64 * kEgSegs), 0, stream, hist, tiles,
+                           keys, total);
+    }
+    hipLaunchKernelGGL(egress_scan_keys_kernel, dim3(1), dim3(kEgScanThreads), 0, stream, eg, total, depth, room, key_start,
+                       key_dropped);
+    hipLaunchKernelGGL(egress_scatter_kernel, dim3(tiles), dim3(64), lds, stream, port, queue, n, eg, kbits, hist, room,
+                       key_start, result, order);
+    return hipGetLastError();
+}
+
 // ---- synthetic config generator (same spec as oracle/nfcs_oracle.c) -----------
 constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
 __host__ __device__ inline uint64_t mix64(uint64_t z) {
