@@ -177,6 +177,24 @@ inline int make_fdb(const ForwardingDatabaseT& fdb, const VlanManagerT& vlans, L
     return make_fdb_from(fdb, vlans, link_up, stp_forwarding, num_ports, out);
 }
 
+// Flood replication for the burst l2_lookup_batch just decided (ChecksumEngine::flood_expand_batch, packet.hpp):
+// the egress work items in the reference's processing order, flood copies included, with the copies' bytes for
+// the caller to wrap in PacketBuffers of its own (BufferPool::allocate_buffer + memcpy, as flood_packet does).
+// This overload over netflow::Packet* was compiled and run against the reference's real types by hand only;
+// the tested path is the same template over netflow_amd::Packet (tests/cpp/flood_test.cpp).
+inline int flood_expand_batch(netflow::Packet* const* pkts, size_t n, const nfcs_fdb* fdb, uint32_t ingress_port,
+                              uint32_t num_ports, const uint32_t* egress_port, const uint8_t* l2_verdict,
+                              const uint16_t* l2_vlan, ChecksumEngine::FloodItems* out) {
+    return detail::on_default_engine([&](ChecksumEngine& e) {
+        return e.flood_expand_batch(pkts, n, fdb, ingress_port, num_ports, egress_port, l2_verdict, l2_vlan, out);
+    });
+}
+inline int flood_expand_batch(const std::vector<netflow::Packet*>& pkts, const nfcs_fdb* fdb, uint32_t ingress_port,
+                              uint32_t num_ports, const uint32_t* egress_port, const uint8_t* l2_verdict,
+                              const uint16_t* l2_vlan, ChecksumEngine::FloodItems* out) {
+    return flood_expand_batch(pkts.data(), pkts.size(), fdb, ingress_port, num_ports, egress_port, l2_verdict, l2_vlan, out);
+}
+
 inline int egress_plan_batch(netflow::Packet* const* pkts, size_t n, const nfcs_egress* eg, const uint32_t* egress_port,
                              uint32_t* ops, uint8_t* queue) {
     return detail::on_default_engine(

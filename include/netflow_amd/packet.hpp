@@ -269,6 +269,27 @@ public:
         return nfcs_fdb_upload(ctx_, fdb);
     }
 
+    // Flood replication (the FLOOD branch of the L2 block plus Switch::flood_packet, switch.hpp:322-324,
+    // 174-206; nfcs_flood_expand_device) for the batch l2_lookup_batch just decided, received on
+    // ingress_port of a switch with num_ports ports: egress_port, l2_verdict and l2_vlan are that call's
+    // outputs (l2_verdict and l2_vlan may both be nullptr: nothing floods). The burst is staged with tail
+    // room for the copies (sized by nfcs_flood_expand_host first, so nothing is cut). out gets the egress
+    // work items in the reference's processing order: per item the source packet's index, the port and the
+    // length; an item with copy_off != FloodItems::kOriginal is a flood copy whose len bytes lie at
+    // copies[copy_off], for the caller to wrap in buffers of its own; the others are the packets themselves.
+    // The packets are not changed. The fdb must be committed and uploaded (upload_fdb).
+    struct FloodItems {
+        static constexpr uint64_t kOriginal = ~0ull;
+        std::vector<uint32_t> src, port, len;  // per item
+        std::vector<uint64_t> copy_off;        // per item: offset into copies, or kOriginal
+        std::vector<uint8_t> copies;           // the copy region, slots of round_up(len, 16) bytes
+        nfcs_flood_totals totals{};
+    };
+    template <class Pkt>
+    int flood_expand_batch(Pkt* const* pkts, size_t n, const nfcs_fdb* fdb, uint32_t ingress_port, uint32_t num_ports,
+                           const uint32_t* egress_port, const uint8_t* l2_verdict, const uint16_t* l2_vlan,
+                           FloodItems* out);
+
     // The egress decision (VlanManager::process_egress + QosManager::classify_packet_to_queue) for a batch
     // whose packet i leaves through egress_port[i] (NFCS_IF_NONE: none), from committed egress ports
     // (nfcs_egress_*; upload_egress first): ops[i] = NFCS_VLAN_POP or NFCS_VLAN_NOP (what process_egress
@@ -706,6 +727,82 @@ int ChecksumEngine::l2_lookup_batch(Pkt* const* pkts, size_t n, const nfcs_fdb* 
     if (verdict && (rc = nfcs_memcpy_d2h(ctx_, verdict, d_status_, n))) return rc;
     if (vlan && (rc = nfcs_memcpy_d2h(ctx_, vlan, dvlan.p, n * sizeof(uint16_t)))) return rc;
     if (learn && (rc = nfcs_memcpy_d2h(ctx_, learn, dlearn.p, n))) return rc;
+    return NFCS_OK;
+}
+
+template <class Pkt>
+int ChecksumEngine::flood_expand_batch(Pkt* const* pkts, size_t n, const nfcs_fdb* fdb, uint32_t ingress_port,
+                                       uint32_t num_ports, const uint32_t* egress_port, const uint8_t* l2_verdict,
+                                       const uint16_t* l2_vlan, FloodItems* out) {
+    if (!out) return NFCS_EINVAL;
+    *out = FloodItems{};
+    if (n == 0) return NFCS_OK;
+    if (!pkts || !fdb || !egress_port || n > 0xFFFFFFFFu || (l2_verdict && !l2_vlan)) return NFCS_EINVAL;
+    std::lock_guard<std::mutex> lock(mu_);
+    const uint32_t m = static_cast<uint32_t>(n);
+    // what the burst calls for, from the lengths alone: the host walk over the layout gather will make
+    std::vector<nfcs_desc> lay(n);
+    size_t frames = 0;
+    for (size_t i = 0; i < n; ++i) {
+        auto* b = pkts[i] ? pkts[i]->get_buffer() : nullptr;
+        const size_t len = b ? b->get_data_length() : 0;
+        lay[i] = nfcs_desc{static_cast<uint32_t>(frames >> 4), static_cast<uint32_t>(len)};
+        frames += (len + 15) & ~size_t(15);
+    }
+    if (frames / 16 > 0xFFFFFFFFu) return NFCS_EINVAL;
+    const uint64_t copy_base = (frames + 127) & ~uint64_t(127);
+    nfcs_flood_totals need{};
+    int rc = nfcs_flood_expand_host(fdb, ingress_port, num_ports, ~0ull, copy_base, 16, lay.data(), m, nullptr, nullptr,
+                                    egress_port, l2_verdict, l2_vlan, 0, nullptr, nullptr, nullptr, &need);
+    if (rc) return rc;
+    const uint64_t arena_bytes = copy_base + need.copy_bytes_needed;
+    if (arena_bytes / 16 > 0xFFFFFFFFu) return NFCS_EINVAL;
+    const uint32_t cap = need.items_needed;
+    if ((rc = reserve(arena_bytes + 16, n))) return rc;
+    gather(pkts, n, 0);
+    DevTmp dport(ctx_, n * sizeof(uint32_t), rc);
+    DevTmp dvlan(ctx_, n * sizeof(uint16_t), rc);
+    DevTmp didesc(ctx_, (size_t)cap * sizeof(nfcs_desc), rc);
+    DevTmp diport(ctx_, (size_t)cap * sizeof(uint32_t), rc);
+    DevTmp disrc(ctx_, (size_t)cap * sizeof(uint32_t), rc);
+    DevTmp dtot(ctx_, sizeof(nfcs_flood_totals), rc);
+    if (rc) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, d_arena_, h_arena_, frames ? frames : 16))) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, d_desc_, h_desc_, n * sizeof(nfcs_desc)))) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, dport.p, egress_port, n * sizeof(uint32_t)))) return rc;
+    if (l2_verdict && (rc = nfcs_memcpy_h2d(ctx_, d_status_, l2_verdict, n))) return rc;
+    if (l2_verdict && (rc = nfcs_memcpy_h2d(ctx_, dvlan.p, l2_vlan, n * sizeof(uint16_t)))) return rc;
+    if ((rc = nfcs_flood_expand_device(ctx_, fdb, ingress_port, num_ports, static_cast<uint8_t*>(d_arena_), arena_bytes,
+                                       copy_base, 16, static_cast<nfcs_desc*>(d_desc_), m, nullptr, nullptr,
+                                       static_cast<uint32_t*>(dport.p),
+                                       l2_verdict ? static_cast<uint8_t*>(d_status_) : nullptr,
+                                       l2_verdict ? static_cast<uint16_t*>(dvlan.p) : nullptr, cap,
+                                       static_cast<nfcs_desc*>(didesc.p), static_cast<uint32_t*>(diport.p),
+                                       static_cast<uint32_t*>(disrc.p), static_cast<nfcs_flood_totals*>(dtot.p), nullptr)))
+        return rc;
+    if ((rc = nfcs_memcpy_d2h(ctx_, &out->totals, dtot.p, sizeof(nfcs_flood_totals)))) return rc;
+    const uint32_t items = out->totals.items;
+    if (items > cap || out->totals.copy_bytes > need.copy_bytes_needed) return NFCS_EHIP;
+    std::vector<nfcs_desc> idesc(items);
+    out->src.resize(items);
+    out->port.resize(items);
+    out->len.resize(items);
+    out->copy_off.resize(items);
+    out->copies.resize(out->totals.copy_bytes);
+    if (items) {
+        if ((rc = nfcs_memcpy_d2h(ctx_, idesc.data(), didesc.p, items * sizeof(nfcs_desc)))) return rc;
+        if ((rc = nfcs_memcpy_d2h(ctx_, out->port.data(), diport.p, items * sizeof(uint32_t)))) return rc;
+        if ((rc = nfcs_memcpy_d2h(ctx_, out->src.data(), disrc.p, items * sizeof(uint32_t)))) return rc;
+    }
+    if (!out->copies.empty() &&
+        (rc = nfcs_memcpy_d2h(ctx_, out->copies.data(), static_cast<uint8_t*>(d_arena_) + copy_base, out->copies.size())))
+        return rc;
+    for (uint32_t k = 0; k < items; ++k) {
+        const uint64_t o = (uint64_t)idesc[k].off16 * 16;
+        out->len[k] = idesc[k].len;
+        out->copy_off[k] = o >= copy_base && out->src[k] < n && o != (uint64_t)lay[out->src[k]].off16 * 16
+                               ? o - copy_base : FloodItems::kOriginal;
+    }
     return NFCS_OK;
 }
 
@@ -1163,6 +1260,13 @@ inline int l2_lookup_batch(Packet* const* pkts, size_t n, const nfcs_fdb* fdb, u
                            uint8_t* learn = nullptr, const uint8_t* rt_verdict = nullptr) {
     return detail::on_default_engine([&](ChecksumEngine& e) {
         return e.l2_lookup_batch(pkts, n, fdb, ingress_port, egress_port, verdict, vlan, learn, rt_verdict);
+    });
+}
+inline int flood_expand_batch(Packet* const* pkts, size_t n, const nfcs_fdb* fdb, uint32_t ingress_port,
+                              uint32_t num_ports, const uint32_t* egress_port, const uint8_t* l2_verdict,
+                              const uint16_t* l2_vlan, ChecksumEngine::FloodItems* out) {
+    return detail::on_default_engine([&](ChecksumEngine& e) {
+        return e.flood_expand_batch(pkts, n, fdb, ingress_port, num_ports, egress_port, l2_verdict, l2_vlan, out);
     });
 }
 inline int flow_keys_batch(Packet* const* pkts, size_t n, nfcs_flow_key* keys,

@@ -483,8 +483,8 @@ NFCS_API int nfcs_acl_eval_device(nfcs_ctx* ctx, const nfcs_acl* acl, const uint
  * learn_mac(src_mac, ingress_port, vlan) would do. Every frame the route lookup marks
  * NFCS_RT_NOT_IPV4 ends here. The symbols of this section were added without changing
  * NFCS_ABI_VERSION (it stays 2): detect them by symbol lookup (dlsym "nfcs_fdb_create").
- * OUT OF SCOPE: packet replication for floods (nfcs_fdb_flood_ports_host names the ports; the copies
- * are the caller's); punting ARP, LLDP and BPDU frames (the reference's lines for LLDP and BPDU are
+ * Flooded packets are replicated by nfcs_flood_expand_device (the next section), which takes this call's
+ * d_verdict and d_vlan. OUT OF SCOPE: punting ARP, LLDP and BPDU frames (the reference's lines for LLDP and BPDU are
  * placeholders; the caller classifies with nfcs_flow_keys_device's EtherType); LACP resolution (elided
  * in the reference); aging; any write to the table from the device. */
 
@@ -616,6 +616,102 @@ NFCS_API int nfcs_l2_lookup_device(nfcs_ctx* ctx, const nfcs_fdb* fdb, uint32_t 
                                    uint32_t n, const uint8_t* d_rt_verdict, uint32_t* d_egress_port,
                                    uint8_t* d_verdict, uint16_t* d_vlan, uint8_t* d_learn, void* stream);
 
+/* ---- Flood replication: the egress item list and the frame copies ---------------------------- */
+
+/* The FLOOD branch of the L2 block plus Switch::flood_packet (switch.hpp:322-324, 174-206) for a burst of
+ * device-resident frames, and with it the compaction of the burst into the egress stage's work items. The
+ * symbols of this section were added without changing NFCS_ABI_VERSION (it stays 2): detect them by symbol
+ * lookup (dlsym "nfcs_flood_expand_device").
+ *
+ * The reference handles packets one after another. A packet with an egress port goes through
+ * process_egress_pipeline as it is. A packet nfcs_l2_lookup_device marks NFCS_L2_FLOOD goes, from
+ * ingress_port on VLAN v = pkt.vlan_id().value_or(native VLAN of the ingress port) (the lookup VLAN,
+ * d_vlan[i] of nfcs_l2_lookup_device), to the ports p < num_ports with p != ingress_port, link up, STP
+ * forwarding and should_forward(ingress_port, p, v), ascending (nfcs_fdb_flood_ports_host): per port the
+ * reference allocates a buffer, copies the frame's len bytes and runs process_egress_pipeline(copy, p); the
+ * original is not sent. A queue that receives unicast packets and flood copies therefore sees them
+ * interleaved by source packet, and within one source packet by ascending port. process_egress only ever
+ * pops a tag, so a copy never grows.
+ *
+ * ONE call turns the burst into the list of egress work items in that order and writes the flood copies
+ * into a copy region [copy_base, arena_bytes) at the tail of the same arena. One descriptor array then
+ * covers originals and copies, and the egress calls run on it unchanged.
+ *
+ * Which packets
+ *  - The unicast port of packet i is nfcs_egress_plan_device's: d_l3_port[i] when that array is given, its
+ *    entry is not NFCS_IF_NONE and, when d_fwd_status is given as well, d_fwd_status[i] & NFCS_ST_FLAG_FWD;
+ *    otherwise d_l2_port[i] when that array is given; otherwise none.
+ *  - NFCS_EINVAL, as in the plan: both port arrays NULL; d_fwd_status without d_l3_port; and d_l2_verdict
+ *    without d_l2_vlan. d_l2_verdict == NULL is legal: nothing floods and the call is the compaction alone.
+ *  - A packet is LIVE when off16*16 + round_up(len, 16) <= copy_base (copy_base <= arena_bytes, else
+ *    NFCS_EINVAL). A packet that is not live yields no item; no source frame can overlap a copy.
+ *  - Live with a unicast port: one item {d_desc[i], port, i}.
+ *  - Live, no unicast port, d_l2_verdict[i] == NFCS_L2_FLOOD: one item {copy descriptor, port, i} per flood
+ *    port of (ingress_port, d_l2_vlan[i], num_ports), ascending; none when no port is eligible. A d_l2_vlan[i]
+ *    above 4095 floods to no port.
+ *  - Every other packet: no item.
+ * Where items and copies go
+ *  - Items are numbered in packet order, within a packet in port order.
+ *  - Copy slots are laid out in item order from copy_base, each round_up(len, copy_align) bytes. copy_align
+ *    is a power of two >= 16 and copy_base a multiple of it; anything else is NFCS_EINVAL.
+ *  - A copy holds the source's whole 16-byte chunks [0, round_up(len, 16)), so the bytes behind len are the
+ *    source's; the rest of its slot is not written. Its len is the source's.
+ *  - An item is a copy exactly when its off16*16 >= copy_base.
+ * Overflow (the reference's allocate_buffer failure, made deterministic)
+ *  - Item k is emitted iff k < cap and the copy region used up to and including item k ends at or before
+ *    arena_bytes. Both are prefix conditions: the emitted items are the first `items` of the full list.
+ *  - items_needed and copy_bytes_needed say what the burst called for (copy_bytes_needed saturates at
+ *    2^64 - 1). n * max(1, min(num_ports, NFCS_L2_MAX_PORTS)) must fit 32 bits, else NFCS_EINVAL.
+ *  - Nothing is written outside [copy_base, arena_bytes) or the first cap item entries, ever.
+ * Padding
+ *  - Entries [items, cap) are written inert: desc {0, 0}, port NFCS_IF_NONE, src NFCS_ITEM_NONE. A caller can
+ *    run plan / VLAN / enqueue over cap entries without a host sync; one that syncs on d_totals runs them
+ *    over `items`. Either way: nfcs_egress_plan_device(..., d_item_desc, m, NULL, NULL, d_item_port, ...),
+ *    nfcs_vlan_device on d_item_desc (it updates the item's length, not d_desc's), then
+ *    nfcs_egress_enqueue_device. d_order then indexes items, and d_item_src maps back to packets.
+ * Other conditions
+ *  - n == 0: NFCS_OK, no launch, nothing written. fdb must be uploaded to ctx. ONE ingress port per call, for
+ *    the reason given at nfcs_l2_lookup_device. cap == 0 lets the three item arrays be NULL.
+ *  - Scratch (one 24-byte record per tile of NFCS_FLOOD_TILE_PKTS packets) belongs to the context, grows on
+ *    demand and is freed by nfcs_ctx_destroy; a failed allocation returns NFCS_ENOMEM and leaves the context
+ *    usable, as the enqueue does.
+ * STILL OUT OF SCOPE: per-port egress ACLs on the copies (as in the egress section); the ingress ACL's
+ * REDIRECT path; interface TX counters. */
+#define NFCS_FLOOD_TILE_PKTS 1024u /* packets per scan tile; SPEED ONLY, tests place sizes around it */
+#define NFCS_ITEM_NONE 0xFFFFFFFFu
+
+typedef struct nfcs_flood_totals {
+    uint32_t items;        /* emitted: entries [0, items) of the item arrays are valid            */
+    uint32_t items_needed; /* what the burst calls for; > items means cap or the region ran out  */
+    uint32_t copies;       /* emitted items that are flood copies                                 */
+    uint32_t flooded;      /* packets taken as floods (live, verdict FLOOD, no unicast port)      */
+    uint64_t copy_bytes;   /* bytes of the copy region the emitted copies occupy (slots)          */
+    uint64_t copy_bytes_needed;
+} nfcs_flood_totals;
+#ifdef __cplusplus
+static_assert(sizeof(nfcs_flood_totals) == 32, "nfcs_flood_totals is a 32-byte record");
+#endif
+
+/* d_arena 16-byte aligned; d_desc, the three port / status / verdict / VLAN arrays as the calls that made
+ * them wrote them; d_item_desc (8-byte aligned), d_item_port, d_item_src: cap entries each; d_totals: one
+ * record, 8-byte aligned. Asynchronous on the stream. Launches (speed only): count per tile, a scan of the
+ * tile sums, emit + copy per tile, padding. */
+NFCS_API int nfcs_flood_expand_device(nfcs_ctx* ctx, const nfcs_fdb* fdb, uint32_t ingress_port, uint32_t num_ports,
+                                      uint8_t* d_arena, uint64_t arena_bytes, uint64_t copy_base, uint32_t copy_align,
+                                      const nfcs_desc* d_desc, uint32_t n, const uint32_t* d_l3_port,
+                                      const uint8_t* d_fwd_status, const uint32_t* d_l2_port,
+                                      const uint8_t* d_l2_verdict, const uint16_t* d_l2_vlan, uint32_t cap,
+                                      nfcs_desc* d_item_desc, uint32_t* d_item_port, uint32_t* d_item_src,
+                                      nfcs_flood_totals* d_totals, void* stream);
+/* The same sequential walk on the CPU (host arrays, same meanings): the definition the kernels equal bit for
+ * bit. It lays the copies out and does not move frame bytes (it takes no arena). fdb must be committed. */
+NFCS_API int nfcs_flood_expand_host(const nfcs_fdb* fdb, uint32_t ingress_port, uint32_t num_ports,
+                                    uint64_t arena_bytes, uint64_t copy_base, uint32_t copy_align,
+                                    const nfcs_desc* desc, uint32_t n, const uint32_t* l3_port,
+                                    const uint8_t* fwd_status, const uint32_t* l2_port, const uint8_t* l2_verdict,
+                                    const uint16_t* l2_vlan, uint32_t cap, nfcs_desc* item_desc, uint32_t* item_port,
+                                    uint32_t* item_src, nfcs_flood_totals* totals);
+
 /* ---- VLAN push / pop + checksum ---------------------------------------- */
 
 /* One VLAN edit per packet as a u32: the operation in bits 30-31, the priority in bits 13-15
@@ -661,8 +757,10 @@ NFCS_API int nfcs_vlan_device(nfcs_ctx* ctx, uint8_t* d_arena, uint64_t arena_by
  * nfcs_egress_enqueue_device gives, per (port, queue), the packet indexes in arrival order with the tail
  * drops counted: what a TX side consumes. The symbols of this section were added without changing
  * NFCS_ABI_VERSION (it stays 2): detect them by symbol lookup (dlsym "nfcs_egress_create").
+ * Flooded packets: NFCS_L2_FLOOD packets have no port and read NFCS_EQ_SKIP when these calls run over the
+ * burst itself; run over the item list of nfcs_flood_expand_device (the section above VLAN) they cover the
+ * flood copies as well.
  * OUT OF SCOPE:
- *  - replicating flooded packets: NFCS_L2_FLOOD packets have no port and read NFCS_EQ_SKIP;
  *  - per-port egress ACLs over a mixed burst: nfcs_acl_eval_device takes one rule list per call. A caller
  *    with one egress list may still pass d_port as that call's d_nh to mask denied packets; that masking
  *    also drops REDIRECT, which the reference's egress path treats as PERMIT;

@@ -73,6 +73,13 @@ L2_PORT_DTYPE = np.dtype([("port_id", "<u4"), ("link_up", "u1"), ("stp_forwardin
                           ("type", "u1"), ("native_vlan", "<u2"), ("pad", "<u2")])
 assert FDB_ENTRY_DTYPE.itemsize == 16 and L2_PORT_DTYPE.itemsize == 12
 
+# flood replication (include/nfcs.h nfcs_flood_expand_*)
+FLOOD_TILE_PKTS = 1024  # NFCS_FLOOD_TILE_PKTS: the scan's tile, speed only
+ITEM_NONE = 0xFFFFFFFF
+FLOOD_TOTALS_DTYPE = np.dtype([("items", "<u4"), ("items_needed", "<u4"), ("copies", "<u4"), ("flooded", "<u4"),
+                               ("copy_bytes", "<u8"), ("copy_bytes_needed", "<u8")])
+assert FLOOD_TOTALS_DTYPE.itemsize == 32
+
 # the egress stage (include/nfcs.h nfcs_egress_*, NFCS_EQ_*)
 QOS_MAX_QUEUES = 8      # classify_packet_to_queue names at most 8 queues from 8 PCP values
 QUEUE_NONE = 0xFF
@@ -202,6 +209,10 @@ def _declare(L):
         "nfcs_fdb_flood_ports_host": ([_vp, _u32, _u32, _u32, _vp, _u32, ctypes.POINTER(_u32)], ctypes.c_int),
         "nfcs_l2_lookup_device": ([_vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp],
                                   ctypes.c_int),
+        "nfcs_flood_expand_device": ([_vp, _vp, _u32, _u32, _vp, _u64, _u64, _u32, _vp, _u32] + [_vp] * 5 + [_u32] +
+                                     [_vp] * 5, ctypes.c_int),
+        "nfcs_flood_expand_host": ([_vp, _u32, _u32, _u64, _u64, _u32, _vp, _u32] + [_vp] * 5 + [_u32] + [_vp] * 4,
+                                   ctypes.c_int),
         "nfcs_egress_create": ([ctypes.POINTER(_vp)], ctypes.c_int),
         "nfcs_egress_destroy": ([_vp], ctypes.c_int),
         "nfcs_egress_set_port": ([_vp, _vp], ctypes.c_int),
@@ -471,6 +482,34 @@ class Fdb:
         _check(lib().nfcs_fdb_flood_ports_host(self.ptr, int(ingress_port), int(vlan), int(num_ports), out.ctypes.data,
                                                len(out), ctypes.byref(n)), "nfcs_fdb_flood_ports_host")
         return out[:n.value].copy()
+
+    def flood_expand_host(self, ingress_port: int, num_ports: int, arena_bytes: int, copy_base: int, copy_align: int,
+                          desc, cap: int, l3_port=None, fwd_status=None, l2_port=None, l2_verdict=None,
+                          l2_vlan=None) -> dict:
+        """The sequential walk behind Engine.flood_expand_device, on the CPU: the burst's egress work items in
+        the reference's processing order, flood copies laid out from copy_base in slots of
+        round_up(len, copy_align). Returns item_desc (cap DESC_DTYPE), item_port and item_src (cap u32 each; the
+        entries past totals["items"] are inert: {0, 0}, IF_NONE, ITEM_NONE) and totals (one
+        FLOOD_TOTALS_DTYPE record). No frame byte is moved."""
+        desc = np.ascontiguousarray(desc, dtype=DESC_DTYPE)
+        n = len(desc)
+        arr = lambda a, dt: None if a is None else np.ascontiguousarray(a, dtype=dt)
+        l3_port, l2_port = arr(l3_port, np.uint32), arr(l2_port, np.uint32)
+        fwd_status, l2_verdict, l2_vlan = arr(fwd_status, np.uint8), arr(l2_verdict, np.uint8), arr(l2_vlan, np.uint16)
+        for a in (l3_port, l2_port, fwd_status, l2_verdict, l2_vlan):
+            if a is not None and len(a) != n:
+                raise NfcsError("flood_expand_host: every per-packet array needs n entries")
+        item_desc, item_port = np.zeros(cap, DESC_DTYPE), np.zeros(cap, np.uint32)
+        item_src, totals = np.zeros(cap, np.uint32), np.zeros(1, FLOOD_TOTALS_DTYPE)
+        dp = lambda a: a.ctypes.data if a is not None and len(a) else None
+        # an array that was given stays given when n is 0: which arrays are given is part of the call
+        given = lambda a: None if a is None else (a.ctypes.data if len(a) else totals.ctypes.data)
+        _check(lib().nfcs_flood_expand_host(self.ptr, int(ingress_port), int(num_ports), int(arena_bytes),
+                                            int(copy_base), int(copy_align), dp(desc), n, given(l3_port),
+                                            given(fwd_status), given(l2_port), given(l2_verdict), given(l2_vlan),
+                                            int(cap), dp(item_desc), dp(item_port), dp(item_src), totals.ctypes.data),
+               "nfcs_flood_expand_host")
+        return {"item_desc": item_desc, "item_port": item_port, "item_src": item_src, "totals": totals[0]}
 
     def close(self):
         if getattr(self, "ptr", None):
@@ -772,6 +811,24 @@ class Engine:
         _check(lib().nfcs_l2_lookup_device(self.ctx, fdb.ptr, int(ingress_port), ptr(arena), arena_bytes, ptr(desc), n,
                                            ptr(rt_verdict), ptr(egress_port), ptr(verdict), ptr(vlan), ptr(learn),
                                            stream), "nfcs_l2_lookup_device")
+
+    def flood_expand_device(self, fdb: "Fdb", ingress_port: int, num_ports: int, arena, arena_bytes: int,
+                            copy_base: int, copy_align: int, desc, n: int, cap: int, item_desc, item_port, item_src,
+                            totals, l3_port=None, fwd_status=None, l2_port=None, l2_verdict=None, l2_vlan=None,
+                            stream=None):
+        """The burst as the egress stage's work items, flood copies included (nfcs_flood_expand_device): per
+        live packet with a unicast port (the plan's rule over l3_port / fwd_status / l2_port) one item, per
+        live packet l2_lookup_device marked L2_FLOOD one item per flood port with a copy of the frame in the
+        region [copy_base, arena_bytes) of the same arena, in slots of round_up(len, copy_align). item_desc
+        (cap DESC_DTYPE), item_port, item_src (cap u32 each) and totals (one FLOOD_TOTALS_DTYPE record) are
+        device buffers; entries past totals.items are written inert. Plan, VLAN and enqueue then run over
+        item_desc / item_port."""
+        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
+        _check(lib().nfcs_flood_expand_device(self.ctx, fdb.ptr, int(ingress_port), int(num_ports), ptr(arena),
+                                              arena_bytes, copy_base, copy_align, ptr(desc), n, ptr(l3_port),
+                                              ptr(fwd_status), ptr(l2_port), ptr(l2_verdict), ptr(l2_vlan), cap,
+                                              ptr(item_desc), ptr(item_port), ptr(item_src), ptr(totals), stream),
+               "nfcs_flood_expand_device")
 
     def egress_plan_device(self, egress: "Egress", arena, arena_bytes: int, desc, n: int, port, ops, queue,
                            l3_port=None, fwd_status=None, l2_port=None, stream=None):

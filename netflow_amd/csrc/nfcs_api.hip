@@ -1390,7 +1390,8 @@ NFCS_API int nfcs_fdb_upload(nfcs_ctx* c, nfcs_fdb* f) {
     auto up16 = [](size_t x) { return (x + 15u) & ~size_t(15); };
     const size_t b_slots = t.slots.size() * sizeof(nfcs::FdbSlot), b_vlans = t.port_vlans.size() * 4u;
     const size_t o_vlans = b_slots, o_native = o_vlans + up16(b_vlans), o_state = o_native + up16(t.ports * 2u);
-    const size_t total = o_state + up16(t.ports) + 16u;
+    const size_t b_rows = t.vlan_ports.size() * 4u, o_rows = o_state + up16(t.ports);
+    const size_t total = o_rows + up16(b_rows) + 16u;
     NFCS_HIP(hipMalloc(&f->d_blob, total));
     f->device = c->di.device;
     hipError_t e = hipMemset(f->d_blob, 0, total);
@@ -1399,6 +1400,7 @@ NFCS_API int nfcs_fdb_upload(nfcs_ctx* c, nfcs_fdb* f) {
         e = hipMemcpy(f->d_blob + o_vlans, t.port_vlans.data(), b_vlans, hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(f->d_blob + o_native, t.port_native.data(), t.ports * 2u, hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(f->d_blob + o_state, t.port_state.data(), t.ports, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(f->d_blob + o_rows, t.vlan_ports.data(), b_rows, hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
         fdb_drop_upload(f);
@@ -1411,6 +1413,8 @@ NFCS_API int nfcs_fdb_upload(nfcs_ctx* c, nfcs_fdb* f) {
     f->dev.port_native = (const uint16_t*)(f->d_blob + o_native);
     f->dev.port_state = f->d_blob + o_state;
     f->dev.ports = t.ports;
+    f->dev.vlan_ports = (const uint32_t*)(f->d_blob + o_rows);
+    f->dev.port_words = t.port_words;
     f->uploaded = true;
     return NFCS_OK;
 }
@@ -1451,6 +1455,59 @@ NFCS_API int nfcs_l2_lookup_device(nfcs_ctx* c, const nfcs_fdb* f, uint32_t ingr
     if (((uintptr_t)d_egress_port & 3u) || ((uintptr_t)d_vlan & 1u)) return NFCS_EINVAL;
     NFCS_HIP(nfcs::launch_l2_lookup(c->di, f->dev, ingress_port, d_arena, arena_bytes, d_desc, n, d_rt_verdict,
                                     d_egress_port, d_verdict, d_vlan, d_learn, pick(c, stream)));
+    return NFCS_OK;
+}
+
+// ---- Flood replication (nfcs_fdb.h: the flood mask and the host walk) and its kernels ---------------
+
+NFCS_API int nfcs_flood_expand_host(const nfcs_fdb* f, uint32_t ingress_port, uint32_t num_ports, uint64_t arena_bytes,
+                                    uint64_t copy_base, uint32_t copy_align, const nfcs_desc* desc, uint32_t n,
+                                    const uint32_t* l3_port, const uint8_t* fwd_status, const uint32_t* l2_port,
+                                    const uint8_t* l2_verdict, const uint16_t* l2_vlan, uint32_t cap,
+                                    nfcs_desc* item_desc, uint32_t* item_port, uint32_t* item_src,
+                                    nfcs_flood_totals* totals) {
+    if (!f || !f->committed) return NFCS_EINVAL;
+    if (!nfcs::flood_args_ok(num_ports, arena_bytes, copy_base, copy_align, n, l3_port, fwd_status, l2_port, l2_verdict,
+                             l2_vlan))
+        return NFCS_EINVAL;
+    if (n == 0) return NFCS_OK;
+    if (!desc || !totals || (cap > 0 && (!item_desc || !item_port || !item_src))) return NFCS_EINVAL;
+    nfcs::flood_expand(f->t, ingress_port, num_ports, arena_bytes, copy_base, copy_align, desc, n, l3_port, fwd_status,
+                       l2_port, l2_verdict, l2_vlan, cap, item_desc, item_port, item_src, totals);
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_flood_expand_device(nfcs_ctx* c, const nfcs_fdb* f, uint32_t ingress_port, uint32_t num_ports,
+                                      uint8_t* d_arena, uint64_t arena_bytes, uint64_t copy_base, uint32_t copy_align,
+                                      const nfcs_desc* d_desc, uint32_t n, const uint32_t* d_l3_port,
+                                      const uint8_t* d_fwd_status, const uint32_t* d_l2_port,
+                                      const uint8_t* d_l2_verdict, const uint16_t* d_l2_vlan, uint32_t cap,
+                                      nfcs_desc* d_item_desc, uint32_t* d_item_port, uint32_t* d_item_src,
+                                      nfcs_flood_totals* d_totals, void* stream) {
+    if (!c || !f || !f->uploaded || f->device != c->di.device) return NFCS_EINVAL;
+    if (!nfcs::flood_args_ok(num_ports, arena_bytes, copy_base, copy_align, n, d_l3_port, d_fwd_status, d_l2_port,
+                             d_l2_verdict, d_l2_vlan))
+        return NFCS_EINVAL;
+    DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    if (n == 0) return NFCS_OK;
+    if (!d_arena || !d_desc || !d_totals || ((uintptr_t)d_arena & 15u) || ((uintptr_t)d_totals & 7u)) return NFCS_EINVAL;
+    if (cap > 0 && (!d_item_desc || !d_item_port || !d_item_src)) return NFCS_EINVAL;
+    if (((uintptr_t)d_l3_port & 3u) || ((uintptr_t)d_l2_port & 3u) || ((uintptr_t)d_l2_vlan & 1u) ||
+        ((uintptr_t)d_item_desc & 7u) || ((uintptr_t)d_item_port & 3u) || ((uintptr_t)d_item_src & 3u))
+        return NFCS_EINVAL;
+    hipStream_t st = pick(c, stream);
+    hipError_t e = acquire_eq(c, nfcs::flood_scratch_words(n), st);  // the enqueue's scratch serves both
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();  // the context stays usable: only this call's scratch is missing
+        return NFCS_ENOMEM;
+    }
+    NFCS_HIP(e);
+    const nfcs::FloodArgs a{d_arena, arena_bytes, copy_base, copy_align, ingress_port, num_ports, n, cap, d_desc,
+                            d_l3_port, d_fwd_status, d_l2_port, d_l2_verdict, d_l2_vlan, d_item_desc, d_item_port,
+                            d_item_src, d_totals};
+    NFCS_HIP(nfcs::launch_flood_expand(c->di, f->dev, a, c->eq_ws, st));
+    NFCS_HIP(release_eq(c, st));
     return NFCS_OK;
 }
 

@@ -222,6 +222,8 @@ struct FdbDev {
     const uint16_t* port_native = nullptr; // ports native VLANs
     const uint32_t* port_vlans = nullptr;  // ports x kL2VlanWords bitmap words
     uint32_t ports = 0;
+    const uint32_t* vlan_ports = nullptr;  // kL2Vlans x port_words: the per-VLAN port bitmap (fdb_flood_word)
+    uint32_t port_words = 0;
 };
 
 hipError_t launch_l2_lookup(const DevInfo& di, const FdbDev& fdb, uint32_t ingress, const uint8_t* arena,
@@ -252,6 +254,38 @@ inline uint64_t egress_scratch_words(uint32_t n, uint32_t keys) {
 hipError_t launch_egress_enqueue(const DevInfo& di, const EgressDev& eg, const uint32_t* port, const uint8_t* queue,
                                  uint32_t n, uint32_t* depth, uint8_t* result, uint32_t* order, uint32_t* key_start,
                                  uint32_t* key_dropped, uint32_t* scratch, hipStream_t stream);
+
+// Flood replication. Tiles of kFloodTile consecutive packets, one 1,024-thread workgroup
+// each, one lane per packet. Scratch: one FloodSum per tile (the count kernel's sums, which the scan turns
+// into each tile's exclusive prefix) and one more for the burst's totals.
+constexpr uint32_t kFloodTile = NFCS_FLOOD_TILE_PKTS;
+static_assert(kFloodTile == 1024u, "a tile is one workgroup of 16 waves, one lane per packet");
+struct alignas(8) FloodSum {
+    uint32_t items, copies, flooded, pad;
+    uint64_t bytes;  // slot bytes, saturating
+};
+static_assert(sizeof(FloodSum) == 24, "six scratch words per tile");
+inline uint64_t flood_scratch_words(uint32_t n) {
+    const uint64_t tiles = ((uint64_t)n + kFloodTile - 1u) / kFloodTile;
+    return (tiles + 1u) * (sizeof(FloodSum) / sizeof(uint32_t));
+}
+struct FloodArgs {
+    uint8_t* arena;
+    uint64_t arena_bytes, copy_base;
+    uint32_t copy_align, ingress, num_ports, n, cap;
+    const nfcs_desc* desc;
+    const uint32_t* l3_port;
+    const uint8_t* fwd_status;
+    const uint32_t* l2_port;
+    const uint8_t* l2_verdict;
+    const uint16_t* l2_vlan;
+    nfcs_desc* item_desc;
+    uint32_t* item_port;
+    uint32_t* item_src;
+    nfcs_flood_totals* totals;
+};
+hipError_t launch_flood_expand(const DevInfo& di, const FdbDev& fdb, const FloodArgs& a, uint32_t* scratch,
+                               hipStream_t stream);
 
 hipError_t launch_gen_config(const DevInfo& di, int config, uint64_t seed, uint64_t first,
                              uint32_t n, uint8_t* arena, uint64_t arena_bytes,

@@ -2808,6 +2808,266 @@ hipError_t launch_egress_enqueue(const DevInfo& di, const EgressDev& eg, const u
     return hipGetLastError();
 }
 
+// ---- Flood replication: the egress item list and the frame copies ----------------
+// nfcs_fdb.h flood_expand is the sequential definition; these kernels equal it bit for bit. Tiles of
+// kFloodTile consecutive packets, one 1,024-thread workgroup each, one lane per packet, XCD-aware order:
+//   1. flood_count_kernel: per packet (items, copies, flooded, slot bytes) by flood_classify — l2_lookup_kernel's
+//      descriptor load, the liveness test against copy_base, the plan's port rule, and for a flooded packet the
+//      population count of its flood mask (fdb_flood_word over the VLAN's row of the per-VLAN port bitmap, the
+//      host walk's function) — summed over the tile into scratch[tile].
+//   2. flood_scan_kernel: ONE workgroup of kFloodScanThreads looping over the tile sums, kFloodScanThreads per
+//      trip with a running carry (no second level): scratch[tile] becomes the tile's exclusive prefix,
+//      scratch[tiles] the burst's totals. The trip count is a function of n alone.
+//   3. flood_emit_kernel: flood_classify again, the tile's exclusive scan (shuffles within a wave, LDS across
+//      the 16 waves), and from the tile's prefix each packet's first item index k0 and first slot offset b0.
+//      Both overflow conditions are monotone in the item index, so a packet's emitted items number
+//      e = min(items, cap - k0, room / slot) in closed form. A unicast packet's lane stores its one item. The
+//      flooded packets of the tile are compacted into LDS (position: the scan of `flooded`), and 64 rows of 16
+//      lanes take them in turn: a row loads up to 6 of its frame's 16-byte chunks per lane ONCE (non-temporal:
+//      the frames are streamed; 1,536 bytes per pass, longer frames make further passes) and walks the set
+//      bits of the mask — at most port_words words of at most 32 bits, a bound fixed by the table — storing
+//      the chunks to each emitted slot, a row's stores to one copy contiguous, and its lane 0 the item record.
+//      Every item store has j < e, so k0 + j < items <= cap; every chunk store is also guarded by its slot's
+//      end <= arena_bytes. The one packet that holds the cut (or the last packet, when nothing is cut) writes
+//      d_totals from its prefix and the scan's last element: no atomic, no accumulation.
+//   4. flood_pad_kernel: entries [items, cap) inert.
+// No position comes from an atomic and no loop ends on data alone.
+#ifndef NFCS_FLOOD_STORE
+#define NFCS_FLOOD_STORE VST_NT  // the copies' store policy (measurement builds: VST_PLAIN / VST_WT), §17
+#endif
+constexpr uint32_t kFloodWaves = kFloodTile / 64u;
+constexpr uint32_t kFloodR = 16, kFloodK = 6;  // a copy row: 16 lanes x 6 chunks
+constexpr uint32_t kFloodRows = kFloodTile / kFloodR;
+constexpr uint32_t kFloodScanThreads = 256;
+
+struct FloodAcc {
+    uint32_t items, copies, flooded;
+    uint64_t bytes;
+};
+DEV FloodAcc flood_zero() { return FloodAcc{0u, 0u, 0u, 0ull}; }
+DEV FloodAcc flood_add(const FloodAcc& a, const FloodAcc& b) {
+    return FloodAcc{a.items + b.items, a.copies + b.copies, a.flooded + b.flooded, flood_sat_add(a.bytes, b.bytes)};
+}
+DEV FloodAcc flood_shfl_up(const FloodAcc& v, uint32_t d) {
+    return FloodAcc{__shfl_up(v.items, d, 64), __shfl_up(v.copies, d, 64), __shfl_up(v.flooded, d, 64),
+                    (uint64_t)__shfl_up((unsigned long long)v.bytes, d, 64)};
+}
+// Inclusive scan across the wave (saturating addition is associative, so the tree's shape does not matter).
+DEV FloodAcc flood_wave_scan(FloodAcc v, uint32_t lane) {
+#pragma unroll
+    for (uint32_t s = 1; s < 64u; s *= 2u) {
+        const FloodAcc t = flood_shfl_up(v, s);
+        if (lane >= s) v = flood_add(t, v);
+    }
+    return v;
+}
+// Exclusive scan across a workgroup of W waves; *total = the workgroup's sum. wsum: W entries of LDS. Every
+// thread of the workgroup calls it.
+template <uint32_t W>
+DEV FloodAcc flood_block_scan(const FloodAcc& own, FloodAcc* wsum, FloodAcc* total) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const FloodAcc inc = flood_wave_scan(own, lane);
+    FloodAcc exc = flood_shfl_up(inc, 1u);
+    if (lane == 0) exc = flood_zero();
+    __syncthreads();  // an earlier call's readers are done with wsum
+    if (lane == 63u) wsum[wave] = inc;
+    __syncthreads();
+    FloodAcc before = flood_zero(), all = flood_zero();
+#pragma unroll
+    for (uint32_t w = 0; w < W; ++w) {
+        const FloodAcc v = wsum[w];
+        if (w < wave) before = flood_add(before, v);
+        all = flood_add(all, v);
+    }
+    *total = all;
+    return flood_add(before, exc);
+}
+
+struct FloodLane {
+    uint2 d;        // the descriptor
+    uint32_t port;  // the unicast port, or NFCS_IF_NONE
+    uint32_t cnt;   // items the packet calls for
+    uint32_t vlan;
+    bool flood;     // taken as a flood (live, verdict FLOOD, no unicast port)
+    uint64_t slot;  // round_up(len, copy_align) for a flooded packet, else 0
+};
+DEV FloodLane flood_classify(const FdbDev& fdb, const FloodArgs& a, uint64_t p) {
+    FloodLane r{make_uint2(0u, 0u), NFCS_IF_NONE, 0u, 0u, false, 0ull};
+    if (p >= a.n) return r;
+    r.d = ((const uint2*)a.desc)[p];
+    const uint64_t off = (uint64_t)r.d.x * 16u;
+    if (off + flood_round_up(r.d.y, 16u) > a.copy_base) return r;  // not live
+    r.port = flood_unicast_port(a.l3_port ? a.l3_port[p] : 0u, a.l3_port != nullptr, a.fwd_status ? a.fwd_status[p] : 0u,
+                                a.fwd_status != nullptr, a.l2_port ? a.l2_port[p] : 0u, a.l2_port != nullptr);
+    if (r.port != NFCS_IF_NONE) {
+        r.cnt = 1u;
+        return r;
+    }
+    if (!a.l2_verdict || a.l2_verdict[p] != NFCS_L2_FLOOD) return r;
+    r.flood = true;
+    r.vlan = a.l2_vlan[p];
+    r.slot = flood_round_up(r.d.y, a.copy_align);
+    if (r.vlan >= kL2Vlans || a.ingress >= fdb.ports) return r;  // should_forward fails for every port
+    const bool in_ok = (fdb.port_vlans[(size_t)a.ingress * kL2VlanWords + (r.vlan >> 5)] >> (r.vlan & 31u)) & 1u;
+    const uint32_t* row = fdb.vlan_ports + (size_t)r.vlan * fdb.port_words;
+    for (uint32_t w = 0; w < fdb.port_words; ++w)  // at most NFCS_L2_MAX_PORTS / 32 words
+        r.cnt += (uint32_t)__popc(fdb_flood_word(row, w, a.ingress, a.num_ports, in_ok));
+    return r;
+}
+DEV FloodAcc flood_acc_of(const FloodLane& l) {
+    return FloodAcc{l.cnt, l.flood ? l.cnt : 0u, l.flood ? 1u : 0u, (uint64_t)l.cnt * l.slot};  // <= 1,023 x 2^33
+}
+DEV FloodAcc flood_load(const FloodSum* s) { return FloodAcc{s->items, s->copies, s->flooded, s->bytes}; }
+DEV void flood_store(FloodSum* s, const FloodAcc& v) {
+    s->items = v.items;
+    s->copies = v.copies;
+    s->flooded = v.flooded;
+    s->pad = 0u;
+    s->bytes = v.bytes;
+}
+
+__global__ __launch_bounds__(kFloodTile) void flood_count_kernel(const FdbDev fdb, const FloodArgs a, uint32_t tiles,
+                                                                 FloodSum* __restrict__ sums) {
+    __shared__ FloodAcc wsum[kFloodWaves];
+    const uint32_t tile = xcd_block_n(tiles);
+    const FloodLane l = flood_classify(fdb, a, (uint64_t)tile * kFloodTile + threadIdx.x);
+    FloodAcc total;
+    (void)flood_block_scan<kFloodWaves>(flood_acc_of(l), wsum, &total);
+    if (threadIdx.x == 0) flood_store(sums + tile, total);
+}
+
+__global__ __launch_bounds__(kFloodScanThreads) void flood_scan_kernel(FloodSum* __restrict__ sums, uint32_t tiles) {
+    __shared__ FloodAcc wsum[kFloodScanThreads / 64u];
+    FloodAcc carry = flood_zero();
+    for (uint32_t base = 0; base < tiles; base += kFloodScanThreads) {  // trips: a function of n alone
+        const uint32_t t = base + threadIdx.x;
+        const FloodAcc own = t < tiles ? flood_load(sums + t) : flood_zero();
+        FloodAcc total;
+        const FloodAcc exc = flood_block_scan<kFloodScanThreads / 64u>(own, wsum, &total);
+        if (t < tiles) flood_store(sums + t, flood_add(carry, exc));
+        carry = flood_add(carry, total);
+    }
+    if (threadIdx.x == 0) flood_store(sums + tiles, carry);
+}
+
+__global__ __launch_bounds__(kFloodTile) void flood_emit_kernel(const FdbDev fdb, const FloodArgs a, uint32_t tiles,
+                                                                const FloodSum* __restrict__ sums) {
+    __shared__ FloodAcc wsum[kFloodWaves];
+    __shared__ uint64_t f_b0[kFloodTile];
+    __shared__ uint32_t f_off16[kFloodTile], f_len[kFloodTile], f_vlan[kFloodTile], f_k0[kFloodTile], f_e[kFloodTile],
+        f_src[kFloodTile];
+    const uint32_t tile = xcd_block_n(tiles);
+    const uint64_t p = (uint64_t)tile * kFloodTile + threadIdx.x;
+    const FloodLane l = flood_classify(fdb, a, p);
+    FloodAcc total;
+    const FloodAcc exc = flood_block_scan<kFloodWaves>(flood_acc_of(l), wsum, &total);
+    const FloodAcc at = flood_add(flood_load(sums + tile), exc);  // what the packets before this one call for
+    // item k is emitted iff k < cap and copy_base + (slot bytes up to and including k) <= arena_bytes: the item
+    // before this packet's first (k0 - 1, region at.bytes) was emitted iff
+    const uint64_t region = flood_sat_add(a.copy_base, at.bytes);
+    const bool open = at.items <= a.cap && region <= a.arena_bytes;
+    uint32_t e = 0;  // how many of this packet's items are emitted
+    if (open && l.cnt) {
+        e = min(l.cnt, a.cap - at.items);
+        if (l.slot) e = (uint32_t)min((uint64_t)e, (a.arena_bytes - region) / l.slot);
+    }
+    if (p < a.n) {
+        if (!l.flood && e) {  // e = 1: at.items < cap
+            ((uint2*)a.item_desc)[at.items] = l.d;
+            a.item_port[at.items] = l.port;
+            a.item_src[at.items] = (uint32_t)p;
+        }
+        if (l.flood) {  // exc.flooded < kFloodTile: its place among the tile's flooded packets
+            f_off16[exc.flooded] = l.d.x;
+            f_len[exc.flooded] = l.d.y;
+            f_vlan[exc.flooded] = l.vlan;
+            f_k0[exc.flooded] = at.items;
+            f_e[exc.flooded] = e;
+            f_b0[exc.flooded] = at.bytes;
+            f_src[exc.flooded] = (uint32_t)p;
+        }
+        // the totals: from the packet that holds the cut, or from the last packet when nothing is cut
+        if (open && (e < l.cnt || p + 1u == a.n)) {
+            const FloodAcc all = flood_load(sums + tiles);
+            nfcs_flood_totals t;
+            t.items = at.items + e;
+            t.items_needed = all.items;
+            t.copies = at.copies + (l.flood ? e : 0u);
+            t.flooded = all.flooded;
+            t.copy_bytes = at.bytes + (l.flood ? (uint64_t)e * l.slot : 0ull);
+            t.copy_bytes_needed = all.bytes;
+            *a.totals = t;
+        }
+    }
+    __syncthreads();
+    // the copies: row `row` takes the tile's flooded packets row, row + kFloodRows, ...
+    const uint32_t nflood = total.flooded, row = threadIdx.x / kFloodR, rl = threadIdx.x % kFloodR;
+    for (uint32_t f = row; f < nflood; f += kFloodRows) {
+        const uint32_t fe = f_e[f];
+        if (fe == 0) continue;  // nothing emitted (then also: every mask word may be empty, the VLAN out of range)
+        const uint32_t len = f_len[f], k0 = f_k0[f], src_i = f_src[f];
+        const uint32_t chunks = (uint32_t)(((uint64_t)len + 15u) >> 4);
+        const uint64_t slot = flood_round_up(len, a.copy_align), first = a.copy_base + f_b0[f];
+        const uint4* src = (const uint4*)(a.arena + (uint64_t)f_off16[f] * 16u);
+        const uint32_t* mrow = fdb.vlan_ports + (size_t)f_vlan[f] * fdb.port_words;  // fe > 0: the VLAN is in range
+        for (uint32_t c0 = 0; c0 == 0 || c0 < chunks; c0 += kFloodR * kFloodK) {  // one pass per 1,536 bytes
+            uint4 v[kFloodK];
+#pragma unroll
+            for (uint32_t s = 0; s < kFloodK; ++s) {
+                const uint32_t c = c0 + rl + kFloodR * s;
+                v[s] = make_uint4(0u, 0u, 0u, 0u);
+                if (c < chunks) v[s] = ld16<1>(src + c);  // live: the frame's chunks lie below copy_base
+            }
+            uint32_t j = 0;
+            for (uint32_t w = 0; w < fdb.port_words && j < fe; ++w) {
+                uint32_t m = fdb_flood_word(mrow, w, a.ingress, a.num_ports, true);
+                for (uint32_t b = 0; b < 32u && m != 0u && j < fe; ++b, ++j) {
+                    const uint32_t port = w * 32u + (uint32_t)__builtin_ctz(m);
+                    m &= m - 1u;
+                    const uint64_t dst = first + (uint64_t)j * slot;  // j < fe: the slot ends inside the arena
+                    if (c0 == 0 && rl == 0) {                         // k0 + j < items <= cap
+                        ((uint2*)a.item_desc)[k0 + j] = make_uint2((uint32_t)(dst >> 4), len);
+                        a.item_port[k0 + j] = port;
+                        a.item_src[k0 + j] = src_i;
+                    }
+                    if (dst + slot <= a.arena_bytes) {
+                        uint4* out = (uint4*)(a.arena + dst);
+#pragma unroll
+                        for (uint32_t s = 0; s < kFloodK; ++s) {
+                            const uint32_t c = c0 + rl + kFloodR * s;
+                            if (c < chunks) vst16<NFCS_FLOOD_STORE>(out + c, v[s]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void flood_pad_kernel(const FloodArgs a) {
+    const uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k >= a.cap || k < a.totals->items) return;
+    ((uint2*)a.item_desc)[k] = make_uint2(0u, 0u);
+    a.item_port[k] = NFCS_IF_NONE;
+    a.item_src[k] = NFCS_ITEM_NONE;
+}
+
+hipError_t launch_flood_expand(const DevInfo& di, const FdbDev& fdb, const FloodArgs& a, uint32_t* scratch,
+                               hipStream_t stream) {
+    (void)di;
+    if (a.n == 0) return hipSuccess;
+    const uint32_t tiles = (uint32_t)(((uint64_t)a.n + kFloodTile - 1u) / kFloodTile);
+    FloodSum* sums = (FloodSum*)scratch;  // tiles + 1 records (flood_scratch_words)
+    hipLaunchKernelGGL(flood_count_kernel, dim3(tiles), dim3(kFloodTile), 0, stream, fdb, a, tiles, sums);
+    hipLaunchKernelGGL(flood_scan_kernel, dim3(1), dim3(kFloodScanThreads), 0, stream, sums, tiles);
+    hipLaunchKernelGGL(flood_emit_kernel, dim3(tiles), dim3(kFloodTile), 0, stream, fdb, a, tiles, sums);
+    if (a.cap) {
+        const uint32_t g = (uint32_t)(((uint64_t)a.cap + kBlock - 1u) / kBlock);
+        hipLaunchKernelGGL(flood_pad_kernel, dim3(g), dim3(kBlock), 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
 // ---- synthetic config generator (same spec as oracle/nfcs_oracle.c) -----------
 constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
 __host__ __device__ inline uint64_t mix64(uint64_t z) {
