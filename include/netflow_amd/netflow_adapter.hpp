@@ -28,6 +28,9 @@
 //   vlan_manager.process_egress(pkt, port) +  netflow_amd::egress_plan_batch(pkts, eg, egress_port, ops, queue), then
 //   qos_manager.enqueue_packet(pkt, port)     vlan_batch(pkts, ops) and egress_enqueue_batch(eg, egress_port, queue, ...)
 //        switch.hpp:113-139                   with eg = netflow_amd::make_egress(vlan_manager, qos_manager, num_ports)
+//   qos_manager.select_packet_to_dequeue(port)  netflow_amd::txq_append_batch(txq, order, key_start, depth, handles)
+//        qos_manager.cpp:197-240              after each egress_enqueue_batch, then txq_dequeue_batch(txq, budget, ...)
+//                                             with txq = netflow_amd::make_txq(qos_manager, num_ports, eg)
 //
 // Every entry returns 0 or a negative NFCS_E* code and never throws (the reference's calls are
 // void / bool and never throw); per-packet outcomes are the NFCS_ST_* status bytes. The bytes
@@ -216,6 +219,28 @@ inline int egress_plan_batch(const std::vector<netflow::Packet*>& pkts, const nf
 template <class VlanManagerT = netflow::VlanManager, class QosManagerT = netflow::QosManager>
 inline int make_egress(const VlanManagerT& vlans, const QosManagerT& qos, uint32_t num_ports, nfcs_egress** out) {
     return make_egress_from(vlans, qos, num_ports, out);
+}
+
+// The TX queues of those ports (nfcs_txq) with QosConfig::scheduler of each port from
+// QosManager::get_port_qos_config: the rings behind enqueue_packet and the scheduler of
+// select_packet_to_dequeue, on `eng`'s device (the process-wide engine by default). eg is what make_egress
+// returned for the same managers. Returns NFCS_OK and the object in *out (nfcs_txq_destroy it before the
+// engine), or a negative NFCS_E* code. The work is make_txq and set_schedulers_from (packet.hpp).
+template <class QosManagerT = netflow::QosManager>
+inline int make_txq(ChecksumEngine& eng, const QosManagerT& qos, uint32_t num_ports, const nfcs_egress* eg,
+                    nfcs_txq** out) {
+    if (!out) return NFCS_EINVAL;
+    *out = nullptr;
+    nfcs_txq* x = nullptr;
+    int rc = eng.make_txq(eg, &x);
+    if (!rc) rc = set_schedulers_from(qos, num_ports, x);
+    if (rc && x) nfcs_txq_destroy(x);
+    else *out = x;
+    return rc;
+}
+template <class QosManagerT = netflow::QosManager>
+inline int make_txq(const QosManagerT& qos, uint32_t num_ports, const nfcs_egress* eg, nfcs_txq** out) {
+    return detail::on_default_engine([&](ChecksumEngine& e) { return make_txq(e, qos, num_ports, eg, out); });
 }
 
 // On an engine of the caller's (another device; one engine per GPU, one host thread each).

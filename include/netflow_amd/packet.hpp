@@ -30,7 +30,12 @@
 //   netflow_amd::egress_plan_batch(Packet* const*, size_t, const nfcs_egress*, egress_port, ops, queue)
 //   netflow_amd::egress_enqueue_batch(const nfcs_egress*, port, queue, n, depth, result, order, key_start, ...)
 // (nfcs_egress_plan_device: the VLAN edit and the queue per packet; nfcs_egress_enqueue_device: per
-// (port, queue) the packet indexes in arrival order, tail drops counted).
+// (port, queue) the packet indexes in arrival order, tail drops counted). The TX queues behind it
+// (QosManager::select_packet_to_dequeue, qos_manager.cpp:197-240), from make_txq and set_schedulers_from
+//   netflow_amd::txq_append_batch(nfcs_txq*, order, key_start, depth, handle, n)
+//   netflow_amd::txq_dequeue_batch(nfcs_txq*, budget, budget_all, depth, tx, tx_cap, tx_queue, tx_start, ...)
+// (nfcs_txq_append_device / nfcs_txq_dequeue_device: rings that persist across bursts, drained per port in
+// the reference's dequeue order).
 //
 // The batch entry points are templates over the packet type: they take this header's Packet or
 // the reference's own netflow::Packet (include/netflow_amd/netflow_adapter.hpp), whose buffers
@@ -311,6 +316,25 @@ public:
         std::lock_guard<std::mutex> lock(mu_);
         return nfcs_egress_upload(ctx_, eg);
     }
+
+    // The TX queues of committed egress ports with a device copy on this engine's device (nfcs_txq_create:
+    // persistent rings per (port, queue) and the scheduler of QosManager::select_packet_to_dequeue). Set the
+    // schedulers with set_schedulers_from; nfcs_txq_destroy the object before the engine.
+    int make_txq(const nfcs_egress* eg, nfcs_txq** out) {
+        std::lock_guard<std::mutex> lock(mu_);
+        return nfcs_txq_create(ctx_, eg, out);
+    }
+    // enqueue_packet's emplace_back for a burst (nfcs_txq_append_device; host arrays, copied in): order,
+    // key_start and depth as egress_enqueue_batch left them, handle[i] = the caller's 64-bit name of packet i
+    // (n of them; a pointer, an index).
+    int txq_append_batch(nfcs_txq* txq, const uint32_t* order, const uint32_t* key_start, const uint32_t* depth,
+                         const uint64_t* handle, size_t n);
+    // Up to budget[port] (budget_all when budget is null) select_packet_to_dequeue calls per port
+    // (nfcs_txq_dequeue_device; host arrays, copied in and out): depth in / out, tx (tx_cap handles: port p's at
+    // tx_start[p] .. tx_start[p+1] in dequeue order), tx_start (ports + 1 u32); tx_queue (tx_cap bytes) and
+    // dequeued (keys u32) optional.
+    int txq_dequeue_batch(nfcs_txq* txq, const uint32_t* budget, uint32_t budget_all, uint32_t* depth, uint64_t* tx,
+                          uint32_t tx_cap, uint8_t* tx_queue, uint32_t* tx_start, uint32_t* dequeued = nullptr);
 
     nfcs_ctx* ctx() const { return ctx_; }
 
@@ -867,6 +891,64 @@ inline int ChecksumEngine::egress_enqueue_batch(const nfcs_egress* eg, const uin
     return NFCS_OK;
 }
 
+inline int ChecksumEngine::txq_append_batch(nfcs_txq* txq, const uint32_t* order, const uint32_t* key_start,
+                                            const uint32_t* depth, const uint64_t* handle, size_t n) {
+    uint32_t keys = 0;
+    if (!txq || nfcs_txq_info(txq, nullptr, &keys, nullptr)) return NFCS_EINVAL;
+    if (n == 0) return NFCS_OK;
+    if (!order || !key_start || !handle || (keys && !depth) || n > 0xFFFFFFFFu) return NFCS_EINVAL;
+    if (key_start[keys] > n) return NFCS_EINVAL;
+    std::lock_guard<std::mutex> lock(mu_);
+    int rc = NFCS_OK;
+    DevTmp dorder(ctx_, n * sizeof(uint32_t), rc);
+    DevTmp dks(ctx_, (keys + 1u) * sizeof(uint32_t), rc);
+    DevTmp ddepth(ctx_, (keys + 1u) * sizeof(uint32_t), rc);
+    DevTmp dhandle(ctx_, n * sizeof(uint64_t), rc);
+    if (rc) return rc;
+    if (key_start[keys] && (rc = nfcs_memcpy_h2d(ctx_, dorder.p, order, key_start[keys] * sizeof(uint32_t)))) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, dks.p, key_start, (keys + 1u) * sizeof(uint32_t)))) return rc;
+    if (keys && (rc = nfcs_memcpy_h2d(ctx_, ddepth.p, depth, keys * sizeof(uint32_t)))) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, dhandle.p, handle, n * sizeof(uint64_t)))) return rc;
+    if ((rc = nfcs_txq_append_device(ctx_, txq, static_cast<uint32_t*>(dorder.p), static_cast<uint32_t*>(dks.p),
+                                     static_cast<uint32_t*>(ddepth.p), static_cast<uint64_t*>(dhandle.p), nullptr,
+                                     static_cast<uint32_t>(n), nullptr)))
+        return rc;
+    return nfcs_stream_sync(ctx_, nullptr);  // the temporaries are freed on return
+}
+
+inline int ChecksumEngine::txq_dequeue_batch(nfcs_txq* txq, const uint32_t* budget, uint32_t budget_all, uint32_t* depth,
+                                             uint64_t* tx, uint32_t tx_cap, uint8_t* tx_queue, uint32_t* tx_start,
+                                             uint32_t* dequeued) {
+    uint32_t ports = 0, keys = 0;
+    if (!txq || !tx_start || nfcs_txq_info(txq, &ports, &keys, nullptr)) return NFCS_EINVAL;
+    if ((keys && !depth) || (tx_cap && !tx)) return NFCS_EINVAL;
+    std::lock_guard<std::mutex> lock(mu_);
+    int rc = NFCS_OK;
+    DevTmp dbudget(ctx_, (ports + 1u) * sizeof(uint32_t), rc);
+    DevTmp ddepth(ctx_, (keys + 1u) * sizeof(uint32_t), rc);
+    DevTmp dtx(ctx_, (static_cast<size_t>(tx_cap) + 1u) * sizeof(uint64_t), rc);
+    DevTmp dtxq(ctx_, static_cast<size_t>(tx_cap) + 1u, rc);
+    DevTmp dstart(ctx_, (ports + 1u) * sizeof(uint32_t), rc);
+    DevTmp ddeq(ctx_, (keys + 1u) * sizeof(uint32_t), rc);
+    if (rc) return rc;
+    if (budget && ports && (rc = nfcs_memcpy_h2d(ctx_, dbudget.p, budget, ports * sizeof(uint32_t)))) return rc;
+    if (keys && (rc = nfcs_memcpy_h2d(ctx_, ddepth.p, depth, keys * sizeof(uint32_t)))) return rc;
+    if ((rc = nfcs_txq_dequeue_device(ctx_, txq, budget ? static_cast<uint32_t*>(dbudget.p) : nullptr, budget_all,
+                                      static_cast<uint32_t*>(ddepth.p), static_cast<uint64_t*>(dtx.p), tx_cap,
+                                      static_cast<uint8_t*>(dtxq.p), static_cast<uint32_t*>(dstart.p),
+                                      static_cast<uint32_t*>(ddeq.p), nullptr)))
+        return rc;
+    if ((rc = nfcs_stream_sync(ctx_, nullptr))) return rc;
+    if ((rc = nfcs_memcpy_d2h(ctx_, tx_start, dstart.p, (ports + 1u) * sizeof(uint32_t)))) return rc;
+    const uint32_t total = tx_start[ports];
+    if (total > tx_cap) return NFCS_EHIP;
+    if (total && (rc = nfcs_memcpy_d2h(ctx_, tx, dtx.p, total * sizeof(uint64_t)))) return rc;
+    if (total && tx_queue && (rc = nfcs_memcpy_d2h(ctx_, tx_queue, dtxq.p, total))) return rc;
+    if (keys && (rc = nfcs_memcpy_d2h(ctx_, depth, ddepth.p, keys * sizeof(uint32_t)))) return rc;
+    if (dequeued && keys && (rc = nfcs_memcpy_d2h(ctx_, dequeued, ddeq.p, keys * sizeof(uint32_t)))) return rc;
+    return NFCS_OK;
+}
+
 // Same interface as netflow::BufferPool (buffer_pool.hpp:57-123: allocate_buffer(payload,
 // headroom), free_buffer(buffer) with the PacketBuffer reference count), except that every
 // buffer up to slot_bytes is a slot of ONE pinned arena (nfcs_host_alloc). update_checksums_batch
@@ -1252,6 +1334,35 @@ inline int egress_enqueue_batch(const nfcs_egress* eg, const uint32_t* port, con
                                 uint32_t* key_dropped = nullptr) {
     return detail::on_default_engine([&](ChecksumEngine& e) {
         return e.egress_enqueue_batch(eg, port, queue, n, depth, result, order, key_start, key_dropped);
+    });
+}
+
+// The schedulers of a TX queue object from the switch's QoS state, by member name:
+// qos.get_port_qos_config(port) yields an optional of a config with `scheduler` (an enum or integer with
+// STRICT_PRIORITY 0, WEIGHTED_ROUND_ROBIN 1, DEFICIT_ROUND_ROBIN 2: QosConfig). Ports 0 .. num_ports - 1 that
+// have a config and lie within the object are set; make_egress_from does not read `scheduler`.
+template <class QosT>
+inline int set_schedulers_from(const QosT& qos, uint32_t num_ports, nfcs_txq* txq) {
+    uint32_t ports = 0;
+    int rc = nfcs_txq_info(txq, &ports, nullptr, nullptr);
+    for (uint32_t p = 0; !rc && p < num_ports && p < ports; ++p) {
+        const auto qc = qos.get_port_qos_config(p);
+        if (qc) rc = nfcs_txq_set_scheduler(txq, p, static_cast<uint32_t>(static_cast<int>(qc->scheduler)));
+    }
+    return rc;
+}
+inline int make_txq(const nfcs_egress* eg, nfcs_txq** out) {
+    return detail::on_default_engine([&](ChecksumEngine& e) { return e.make_txq(eg, out); });
+}
+inline int txq_append_batch(nfcs_txq* txq, const uint32_t* order, const uint32_t* key_start, const uint32_t* depth,
+                            const uint64_t* handle, size_t n) {
+    return detail::on_default_engine(
+        [&](ChecksumEngine& e) { return e.txq_append_batch(txq, order, key_start, depth, handle, n); });
+}
+inline int txq_dequeue_batch(nfcs_txq* txq, const uint32_t* budget, uint32_t budget_all, uint32_t* depth, uint64_t* tx,
+                             uint32_t tx_cap, uint8_t* tx_queue, uint32_t* tx_start, uint32_t* dequeued = nullptr) {
+    return detail::on_default_engine([&](ChecksumEngine& e) {
+        return e.txq_dequeue_batch(txq, budget, budget_all, depth, tx, tx_cap, tx_queue, tx_start, dequeued);
     });
 }
 

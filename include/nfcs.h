@@ -764,8 +764,9 @@ NFCS_API int nfcs_vlan_device(nfcs_ctx* ctx, uint8_t* d_arena, uint64_t arena_by
  *  - per-port egress ACLs over a mixed burst: nfcs_acl_eval_device takes one rule list per call. A caller
  *    with one egress list may still pass d_port as that call's d_nh to mask denied packets; that masking
  *    also drops REDIRECT, which the reference's egress path treats as PERMIT;
- *  - scheduling and dequeue (strict priority, WRR, DRR, token buckets): the TX side's, which subtracts
- *    what it dequeues from d_depth;
+ *  - token buckets and rate limits: the reference's are placeholders (should_transmit's bucket is a TODO,
+ *    update_token_buckets is empty). Scheduling and dequeue are the TX queues' section below, which
+ *    subtracts what it dequeues from d_depth;
  *  - interface TX counters. */
 
 /* classify_packet_to_queue can name at most 8 distinct queues from the 8 PCP values, so a port has at most
@@ -877,6 +878,97 @@ NFCS_API int nfcs_egress_enqueue_device(nfcs_ctx* ctx, const nfcs_egress* eg, co
 NFCS_API int nfcs_egress_enqueue_host(const nfcs_egress* eg, const uint32_t* port, const uint8_t* queue,
                                       uint32_t n, uint32_t* depth, uint8_t* result, uint32_t* order,
                                       uint32_t* key_start, uint32_t* key_dropped);
+
+/* ---- TX queues: persistent rings and the dequeue scheduler --------------------------------------- */
+
+/* The queues behind QosManager::enqueue_packet (qos_manager.cpp:111-153) and the scheduler of
+ * QosManager::select_packet_to_dequeue / dequeue_packet (155-240): one ring of 64-bit handles per (port,
+ * queue) that lives on the device across bursts, nfcs_txq_append_device (the burst's emplace_back, after
+ * nfcs_egress_enqueue_device) and nfcs_txq_dequeue_device (`budget` select_packet_to_dequeue calls per
+ * port, into a per-port TX list in the reference's dequeue order). The symbols of this section were added
+ * without changing NFCS_ABI_VERSION (it stays 2): detect them by symbol lookup (dlsym "nfcs_txq_create").
+ * REPRODUCED QUIRKS of the reference:
+ *  - should_transmit is true for every non-empty queue (its token bucket is a TODO), so rate_limits_kbps
+ *    has no effect there and none here;
+ *  - WEIGHTED_ROUND_ROBIN and DEFICIT_ROUND_ROBIN share one branch that never reads queue_weights: both
+ *    are plain round-robin over the non-empty queues, starting behind the port's last-serviced queue;
+ *  - configure_port_qos sets the last-serviced queue to 0, so the first round-robin dequeue of a fresh
+ *    port comes from queue 1 when that is non-empty.
+ * The object is state: calls on one nfcs_txq from two streams (or threads) at once are the caller's error.
+ * OUT OF SCOPE: token buckets and rate limits; weights having any effect; interface TX counters (the
+ * handle is opaque; a caller using descriptor handles can sum len from d_tx); queue contents surviving a
+ * re-commit of the egress table (a re-commit wants a new nfcs_txq); per-port egress ACLs. */
+enum { NFCS_SCHED_STRICT_PRIORITY = 0, NFCS_SCHED_WRR = 1, NFCS_SCHED_DRR = 2 };
+typedef struct nfcs_txq nfcs_txq;
+
+/* Snapshots the committed `eg` (else NFCS_EINVAL): ports, keys = ports * NFCS_QOS_MAX_QUEUES, and each
+ * port's has_qos, num_queues and max_queue_depth; later changes to eg do not reach the object, and nothing
+ * in eg is edited. Per key k it holds a ring of cap[k] = max_queue_depth handles for every queue the port
+ * has (0 for the others and for ports without QoS), head[k] in [0, cap[k]), and per port the last-serviced
+ * queue, 0 at first. It stores no tail: a queue's tail is head + depth, depth being the caller's d_depth[k],
+ * the array the enqueue chains. Two independent copies of the state: the _host calls advance a host copy,
+ * the _device calls a device copy on ctx's device, absent when ctx is NULL (device calls then return
+ * NFCS_EINVAL). Scratch (per key and per port) is sized here and belongs to the object. A failed
+ * allocation returns NFCS_ENOMEM and leaks nothing. Destroy the object before the ctx. */
+NFCS_API int nfcs_txq_create(nfcs_ctx* ctx, const nfcs_egress* eg, nfcs_txq** out);
+NFCS_API int nfcs_txq_destroy(nfcs_txq* txq);
+/* QosConfig::scheduler of one port (default NFCS_SCHED_STRICT_PRIORITY, as QosConfig's). NFCS_EINVAL for
+ * port_id >= ports or sched > 2. Updates both copies, the device copy synchronously: call it while the
+ * object is idle. */
+NFCS_API int nfcs_txq_set_scheduler(nfcs_txq* txq, uint32_t port_id, uint32_t sched);
+/* Heads and last-serviced queues to 0 on both copies (configure_port_qos); synchronous. The caller zeroes
+ * its depth arrays. */
+NFCS_API int nfcs_txq_reset(nfcs_txq* txq);
+/* *ports, *keys and *ring_slots (the sum of cap); each may be NULL. */
+NFCS_API int nfcs_txq_info(const nfcs_txq* txq, uint32_t* ports, uint32_t* keys, uint64_t* ring_slots);
+/* The state of one copy: head (keys u32) and last (ports bytes), each may be NULL. The device call waits
+ * for `stream` (NULL: the context's) and downloads. */
+NFCS_API int nfcs_txq_state_device(nfcs_txq* txq, uint32_t* head, uint8_t* last, void* stream);
+NFCS_API int nfcs_txq_state_host(const nfcs_txq* txq, uint32_t* head, uint8_t* last);
+
+/* enqueue_packet's emplace_back for the burst. Runs after nfcs_egress_enqueue_device of the same burst,
+ * with that call's d_order and d_key_start and the d_depth it left, before any other enqueue or dequeue on
+ * that depth array. For key k with cnt = key_start[k+1] - key_start[k] and before = depth[k] - cnt, for j
+ * in [0, cnt):   ring[k][(head[k] + before + j) mod cap[k]] = handle(order[key_start[k] + j]).
+ * The handle of packet i is d_handle[i] when that array is given, otherwise its descriptor's bits,
+ * off16 | (uint64_t)len << 32, as they are when the call runs (after the VLAN edit). head and depth are
+ * only read. A key with cap[k] == 0, depth[k] < cnt or depth[k] > cap[k] is inconsistent input and appends
+ * nothing; entries of order that are >= n are skipped; no input carries a store outside the rings.
+ * n == 0 returns NFCS_OK without a launch; d_handle and d_desc both NULL: NFCS_EINVAL. One kernel, one
+ * lane per enqueued position, asynchronous on the stream. */
+NFCS_API int nfcs_txq_append_device(nfcs_ctx* ctx, nfcs_txq* txq, const uint32_t* d_order,
+                                    const uint32_t* d_key_start, const uint32_t* d_depth, const uint64_t* d_handle,
+                                    const nfcs_desc* d_desc, uint32_t n, void* stream);
+NFCS_API int nfcs_txq_append_host(nfcs_txq* txq, const uint32_t* order, const uint32_t* key_start,
+                                  const uint32_t* depth, const uint64_t* handle, const nfcs_desc* desc, uint32_t n);
+
+/* select_packet_to_dequeue, up to budget[port] times per port (budget_all when budget is NULL), ports
+ * ascending; a port stops at the first nullopt, everything stops once tx_cap handles have been written.
+ *   d_depth     keys u32, IN/OUT: falls by what was taken; the depth used is min(depth[k], cap[k])
+ *   d_tx        tx_cap handles: port p's are d_tx[d_tx_start[p] .. d_tx_start[p+1]) in dequeue order;
+ *               entries past the total are left alone
+ *   d_tx_queue  optional (NULL) tx_cap bytes: the queue each entry came from
+ *   d_tx_start  ports + 1 u32; d_tx_start[ports] is the total
+ *   d_dequeued  optional (NULL) keys u32: this call's count per key (QueueStats::packets_dequeued)
+ * head[k] advances by what was taken, mod cap. Strict priority: each call takes the lowest-numbered
+ * non-empty queue and leaves last-serviced alone. WRR and DRR, alike: each call tests the queues
+ * (last + 1 + i) % num_queues for i = 0..num_queues-1, takes the first non-empty one and sets last to it.
+ * A port without a QoS config dequeues nothing. The device call is three kernels (plan, gather, commit),
+ * asynchronous on the stream, computing the closed form of that walk; no position comes
+ * from an atomic, so the same call on the same state gives the same d_tx. */
+NFCS_API int nfcs_txq_dequeue_device(nfcs_ctx* ctx, nfcs_txq* txq, const uint32_t* d_budget, uint32_t budget_all,
+                                     uint32_t* d_depth, uint64_t* d_tx, uint32_t tx_cap, uint8_t* d_tx_queue,
+                                     uint32_t* d_tx_start, uint32_t* d_dequeued, void* stream);
+NFCS_API int nfcs_txq_dequeue_host(nfcs_txq* txq, const uint32_t* budget, uint32_t budget_all, uint32_t* depth,
+                                   uint64_t* tx, uint32_t tx_cap, uint8_t* tx_queue, uint32_t* tx_start,
+                                   uint32_t* dequeued);
+/* The closed form the kernels compute, for one port on the CPU: with num_queues (1..8) queues of the given
+ * depths, scheduler sched and last-serviced queue last, `budget` select_packet_to_dequeue calls take
+ * take[q] packets of queue q (num_queues entries) and leave *new_last; seq (optional, seq_cap bytes)
+ * receives the queue of each call in order, placed by rank. Pure host code; tests hold it to the walk. */
+NFCS_API int nfcs_txq_closed_form_host(uint32_t sched, uint32_t num_queues, uint32_t last, const uint32_t* depth,
+                                       uint32_t budget, uint32_t* take, uint32_t* new_last, uint8_t* seq,
+                                       uint32_t seq_cap);
 
 /* ---- flow-key extract + hash -------------------------------------------- */
 

@@ -89,6 +89,8 @@ EGRESS_PORT_DTYPE = np.dtype([("port_id", "<u4"), ("has_vlan_config", "u1"), ("t
                               ("has_qos", "u1"), ("native_vlan", "<u2"), ("num_queues", "u1"), ("pad", "u1"),
                               ("max_queue_depth", "<u4")])
 assert EGRESS_PORT_DTYPE.itemsize == 16
+# the TX queues (include/nfcs.h nfcs_txq_*, NFCS_SCHED_*); WRR and DRR are the reference's one plain round-robin
+SCHED_STRICT_PRIORITY, SCHED_WRR, SCHED_DRR = range(3)
 
 NEXTHOP_DTYPE = np.dtype([("dst_mac", "u1", (6,)), ("src_mac", "u1", (6,))])
 FLOW_KEY_DTYPE = np.dtype([("hash", "<u4"), ("vlan_id", "<u2"), ("ethertype", "<u2"),
@@ -224,6 +226,18 @@ def _declare(L):
         "nfcs_egress_enqueue_host": ([_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
         "nfcs_egress_plan_device": ([_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
         "nfcs_egress_enqueue_device": ([_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+        "nfcs_txq_create": ([_vp, _vp, ctypes.POINTER(_vp)], ctypes.c_int),
+        "nfcs_txq_destroy": ([_vp], ctypes.c_int),
+        "nfcs_txq_set_scheduler": ([_vp, _u32, _u32], ctypes.c_int),
+        "nfcs_txq_reset": ([_vp], ctypes.c_int),
+        "nfcs_txq_info": ([_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u64)], ctypes.c_int),
+        "nfcs_txq_state_device": ([_vp, _vp, _vp, _vp], ctypes.c_int),
+        "nfcs_txq_state_host": ([_vp, _vp, _vp], ctypes.c_int),
+        "nfcs_txq_append_device": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp], ctypes.c_int),
+        "nfcs_txq_append_host": ([_vp, _vp, _vp, _vp, _vp, _vp, _u32], ctypes.c_int),
+        "nfcs_txq_dequeue_device": ([_vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp], ctypes.c_int),
+        "nfcs_txq_dequeue_host": ([_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp], ctypes.c_int),
+        "nfcs_txq_closed_form_host": ([_u32, _u32, _u32, _vp, _u32, _vp, ctypes.POINTER(_u32), _vp, _u32], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         # a measurement build of an earlier round (NFCS_LIB, A/B runs) may lack a later entry point;
@@ -619,6 +633,122 @@ class Egress:
             pass
 
 
+class TxQueues:
+    """The TX queues of a committed Egress (nfcs_txq): one ring of 64-bit handles per (port, queue) and the
+    scheduler of QosManager::select_packet_to_dequeue. With an engine it holds a device copy beside the host
+    copy (Engine.txq_append_device / txq_dequeue_device advance it); without one it is host-only. It
+    snapshots the Egress at creation; close it before the engine."""
+
+    def __init__(self, egress: "Egress", engine: "Engine | None" = None):
+        p = _vp()
+        _check(lib().nfcs_txq_create(engine.ctx if engine is not None else None, egress.ptr, ctypes.byref(p)),
+               "nfcs_txq_create")
+        self.ptr = p.value
+        self.ports, self.keys, self.ring_slots = self.info()
+
+    def set_scheduler(self, port_id: int, sched: int):
+        """QosConfig::scheduler of one port (SCHED_*; default SCHED_STRICT_PRIORITY), on both copies."""
+        if not (0 <= int(port_id) <= 0xFFFFFFFF and 0 <= int(sched) <= 0xFFFFFFFF):
+            raise NfcsError("nfcs_txq_set_scheduler: invalid argument")
+        _check(lib().nfcs_txq_set_scheduler(self.ptr, int(port_id), int(sched)), "nfcs_txq_set_scheduler")
+        return self
+
+    def reset(self):
+        """Heads and last-serviced queues to 0 on both copies (configure_port_qos)."""
+        _check(lib().nfcs_txq_reset(self.ptr), "nfcs_txq_reset")
+        return self
+
+    def info(self) -> tuple[int, int, int]:
+        """(ports, keys, ring_slots)."""
+        a, b, c = _u32(), _u32(), _u64()
+        _check(lib().nfcs_txq_info(self.ptr, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "nfcs_txq_info")
+        return int(a.value), int(b.value), int(c.value)
+
+    def _state(self, fn, what, *extra):
+        head, last = np.zeros(self.keys, np.uint32), np.zeros(self.ports, np.uint8)
+        dp = lambda a: a.ctypes.data if len(a) else None
+        _check(fn(self.ptr, dp(head), dp(last), *extra), what)
+        return head, last
+
+    def state_host(self) -> tuple[np.ndarray, np.ndarray]:
+        """(head per key, last-serviced queue per port) of the host copy."""
+        return self._state(lib().nfcs_txq_state_host, "nfcs_txq_state_host")
+
+    def state_device(self, stream=None) -> tuple[np.ndarray, np.ndarray]:
+        """The same of the device copy, after waiting for the stream."""
+        return self._state(lib().nfcs_txq_state_device, "nfcs_txq_state_device", stream)
+
+    def append_host(self, order, key_start, depth, n: int, handle=None, desc=None):
+        """enqueue_packet's emplace_back for a burst of n packets on the host copy: order / key_start /
+        depth as enqueue_host left them; handle (n u64) or desc (n DESC_DTYPE) names the packets."""
+        order = np.ascontiguousarray(order, dtype=np.uint32)
+        key_start = np.ascontiguousarray(key_start, dtype=np.uint32)
+        depth = np.ascontiguousarray(depth, dtype=np.uint32)
+        if len(key_start) != self.keys + 1 or len(depth) != self.keys or len(order) < int(key_start[-1]):
+            raise NfcsError("append_host: key_start needs keys + 1 entries, depth keys, order key_start[keys]")
+        if handle is not None:
+            handle = np.ascontiguousarray(handle, dtype=np.uint64)
+        if desc is not None:
+            desc = np.ascontiguousarray(desc, dtype=DESC_DTYPE)
+        if any(a is not None and len(a) < n for a in (handle, desc)):
+            raise NfcsError("append_host: handle / desc need n entries")
+        dp = lambda a: a.ctypes.data if a is not None and len(a) else None
+        _check(lib().nfcs_txq_append_host(self.ptr, dp(order), key_start.ctypes.data, dp(depth), dp(handle), dp(desc),
+                                          int(n)), "nfcs_txq_append_host")
+        return self
+
+    def dequeue_host(self, depth, tx_cap: int, budget=None, budget_all: int = 0) -> dict:
+        """The sequential dequeue on the host copy: up to budget[port] (or budget_all) select_packet_to_dequeue
+        calls per port, ports ascending, at most tx_cap handles. Returns depth (after), tx (the handles
+        dequeued, port-major in dequeue order), tx_queue, tx_start (ports + 1) and dequeued (per key)."""
+        depth = np.array(depth, dtype=np.uint32)
+        if len(depth) != self.keys:
+            raise NfcsError("dequeue_host: depth needs one entry per key")
+        if budget is not None:
+            budget = np.ascontiguousarray(budget, dtype=np.uint32)
+            if len(budget) != self.ports:
+                raise NfcsError("dequeue_host: budget needs one entry per port")
+        tx, tx_queue = np.zeros(tx_cap, np.uint64), np.zeros(tx_cap, np.uint8)
+        tx_start, dequeued = np.zeros(self.ports + 1, np.uint32), np.zeros(self.keys, np.uint32)
+        dp = lambda a: a.ctypes.data if a is not None and len(a) else None
+        _check(lib().nfcs_txq_dequeue_host(self.ptr, dp(budget), int(budget_all), dp(depth), dp(tx), int(tx_cap),
+                                           dp(tx_queue), tx_start.ctypes.data, dp(dequeued)), "nfcs_txq_dequeue_host")
+        total = int(tx_start[self.ports])
+        return {"depth": depth, "tx": tx[:total], "tx_queue": tx_queue[:total], "tx_start": tx_start,
+                "dequeued": dequeued}
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            lib().nfcs_txq_destroy(self.ptr)
+            self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def txq_closed_form_host(sched: int, depth, last: int, budget: int, want_seq: bool = True):
+    """The closed form of the dequeue for one port (nfcs_txq_closed_form_host): (take per queue, new
+    last-serviced queue, the queue of each select_packet_to_dequeue call in order, or None without want_seq)."""
+    depth = np.ascontiguousarray(depth, dtype=np.uint32)
+    nq = len(depth)
+    take, new_last = np.zeros(nq, np.uint32), _u32()
+    cap = int(min(int(depth.sum(dtype=np.uint64)), budget)) if want_seq else 0
+    seq = np.full(cap, QUEUE_NONE, np.uint8)
+    _check(lib().nfcs_txq_closed_form_host(int(sched), nq, int(last), depth.ctypes.data if nq else None, int(budget),
+                                           take.ctypes.data if nq else None, ctypes.byref(new_last),
+                                           seq.ctypes.data if cap else None, cap), "nfcs_txq_closed_form_host")
+    return take, int(new_last.value), seq if want_seq else None
+
+
 class DeviceBuffer:
     """A raw device allocation owned by an Engine (no torch types involved)."""
 
@@ -851,6 +981,24 @@ class Engine:
         _check(lib().nfcs_egress_enqueue_device(self.ctx, egress.ptr, ptr(port), ptr(queue), n, ptr(depth), ptr(result),
                                                 ptr(order), ptr(key_start), ptr(key_dropped), stream),
                "nfcs_egress_enqueue_device")
+
+    def txq_append_device(self, txq: "TxQueues", order, key_start, depth, n: int, handle=None, desc=None, stream=None):
+        """enqueue_packet's emplace_back for the burst on the device copy of txq, after egress_enqueue_device
+        with that call's order / key_start and the depth it left: the handles of the enqueued packets
+        (handle, n u64, or the descriptor bits of desc as they are now) go to their rings."""
+        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
+        _check(lib().nfcs_txq_append_device(self.ctx, txq.ptr, ptr(order), ptr(key_start), ptr(depth), ptr(handle),
+                                            ptr(desc), n, stream), "nfcs_txq_append_device")
+
+    def txq_dequeue_device(self, txq: "TxQueues", depth, tx, tx_cap: int, tx_start, budget=None, budget_all: int = 0,
+                           tx_queue=None, dequeued=None, stream=None):
+        """select_packet_to_dequeue up to budget[port] (ports u32) or budget_all times per port on the device
+        copy: depth (keys u32, in/out), tx (tx_cap u64: port p's handles at tx_start[p]..tx_start[p+1] in
+        dequeue order), tx_start (ports + 1 u32); tx_queue (tx_cap bytes) and dequeued (keys u32) optional."""
+        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
+        _check(lib().nfcs_txq_dequeue_device(self.ctx, txq.ptr, ptr(budget), int(budget_all), ptr(depth), ptr(tx),
+                                             int(tx_cap), ptr(tx_queue), ptr(tx_start), ptr(dequeued), stream),
+               "nfcs_txq_dequeue_device")
 
     def vlan_device(self, arena, arena_bytes: int, desc, n: int, ops=None, op_all: int = 0,
                     caps=None, cap_all: int = 0, status=None, stream=None):

@@ -1676,6 +1676,260 @@ NFCS_API int nfcs_egress_enqueue_device(nfcs_ctx* c, const nfcs_egress* g, const
     return NFCS_OK;
 }
 
+// ---- TX queues (nfcs_txq.h: tables, host state, the walks and the closed form) and their kernels ------
+}  // extern "C"
+
+struct nfcs_txq {
+    nfcs::TxqTables t;
+    nfcs::TxqState h;  // the host copy
+    // the device copy (absent for a host-only object): tables, heads, last and scratch in d_blob, the rings
+    // in d_ring
+    nfcs_ctx* ctx = nullptr;
+    int device = -1;
+    uint8_t* d_blob = nullptr;
+    uint8_t* d_ring = nullptr;
+    size_t state_off = 0, state_bytes = 0;  // head and last within d_blob (what nfcs_txq_reset zeroes)
+    nfcs::TxqDev dev;
+};
+
+namespace {
+void txq_free_device(nfcs_txq* x) {
+    if (x->d_blob || x->d_ring) {
+        DeviceGuard dg_(x->device);
+        if (dg_.err == hipSuccess) {
+            if (x->d_blob) (void)hipFree(x->d_blob);
+            if (x->d_ring) (void)hipFree(x->d_ring);
+        }
+    }
+    x->d_blob = x->d_ring = nullptr;
+    x->dev = nfcs::TxqDev{};
+}
+
+// Lays the device copy out in one allocation (every part 16-byte aligned) plus the rings, and uploads the
+// tables; heads, last and scratch start as zero.
+int txq_make_device(nfcs_ctx* c, nfcs_txq* x) {
+    const nfcs::TxqTables& t = x->t;
+    size_t off = 0;
+    auto part = [&off](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 15u) & ~(size_t)15u;
+        return at;
+    };
+    const size_t o_port = part((size_t)t.ports * sizeof(nfcs::TxqPort));
+    const size_t o_base = part(((size_t)t.keys + 1u) * sizeof(uint64_t));
+    const size_t o_head = part((size_t)t.keys * 4u);
+    const size_t o_last = part((size_t)t.ports * 4u);
+    const size_t o_take = part((size_t)t.keys * 4u);
+    const size_t o_elem = part(((size_t)t.keys + 1u) * 4u);
+    const size_t o_txs = part(((size_t)t.ports + 1u) * 4u);
+    const size_t o_nl = part((size_t)t.ports * 4u);
+    if (t.ring_slots > (SIZE_MAX >> 4)) return NFCS_ENOMEM;
+    DeviceGuard dg_(c->di.device);
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    x->device = c->di.device;
+    hipError_t e = hipMalloc(&x->d_blob, off + 16u);
+    if (e == hipSuccess) e = hipMalloc(&x->d_ring, (size_t)t.ring_slots * 8u + 16u);
+    if (e == hipSuccess) e = hipMemset(x->d_blob, 0, off + 16u);
+    if (e == hipSuccess) e = hipMemset(x->d_ring, 0, (size_t)t.ring_slots * 8u + 16u);
+    if (e == hipSuccess && t.ports)
+        e = hipMemcpy(x->d_blob + o_port, t.port.data(), (size_t)t.ports * sizeof(nfcs::TxqPort), hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(x->d_blob + o_base, t.ring_base.data(), ((size_t)t.keys + 1u) * sizeof(uint64_t),
+                      hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        txq_free_device(x);
+        if (e == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            return NFCS_ENOMEM;
+        }
+        return hip_fail(e);
+    }
+    x->state_off = o_head;
+    x->state_bytes = o_take - o_head;  // head, then last
+    nfcs::TxqDev& d = x->dev;
+    d.port = (const uint4*)(x->d_blob + o_port);
+    d.ring_base = (const uint64_t*)(x->d_blob + o_base);
+    d.ring = (uint64_t*)x->d_ring;
+    d.head = (uint32_t*)(x->d_blob + o_head);
+    d.last = (uint32_t*)(x->d_blob + o_last);
+    d.take = (uint32_t*)(x->d_blob + o_take);
+    d.elem_start = (uint32_t*)(x->d_blob + o_elem);
+    d.tx_start = (uint32_t*)(x->d_blob + o_txs);
+    d.new_last = (uint32_t*)(x->d_blob + o_nl);
+    d.ports = t.ports;
+    d.keys = t.keys;
+    d.ring_slots = t.ring_slots;
+    x->ctx = c;
+    return NFCS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+NFCS_API int nfcs_txq_create(nfcs_ctx* c, const nfcs_egress* g, nfcs_txq** out) {
+    if (!out) return NFCS_EINVAL;
+    *out = nullptr;
+    if (!g || !g->committed) return NFCS_EINVAL;
+    nfcs_txq* x = new (std::nothrow) nfcs_txq();
+    if (!x) return NFCS_ENOMEM;
+    try {
+        nfcs::txq_compile(g->t, x->t);
+        nfcs::txq_state_init(x->t, x->h);
+    } catch (...) {
+        delete x;
+        return NFCS_ENOMEM;
+    }
+    if (c) {
+        const int rc = txq_make_device(c, x);
+        if (rc != NFCS_OK) {
+            delete x;
+            return rc;
+        }
+    }
+    *out = x;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_txq_destroy(nfcs_txq* x) {
+    if (!x) return NFCS_EINVAL;
+    txq_free_device(x);
+    delete x;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_txq_set_scheduler(nfcs_txq* x, uint32_t port_id, uint32_t sched) {
+    if (!x || port_id >= x->t.ports || sched > NFCS_SCHED_DRR) return NFCS_EINVAL;
+    if (x->ctx) {
+        DeviceGuard dg_(x->device);
+        if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+        nfcs::TxqPort rec = x->t.port[port_id];
+        rec.sched = sched;
+        NFCS_HIP(hipMemcpy((uint8_t*)x->dev.port + (size_t)port_id * sizeof(rec), &rec, sizeof(rec), hipMemcpyHostToDevice));
+        NFCS_HIP(hipDeviceSynchronize());
+    }
+    x->t.port[port_id].sched = sched;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_txq_reset(nfcs_txq* x) {
+    if (!x) return NFCS_EINVAL;
+    if (x->ctx) {
+        DeviceGuard dg_(x->device);
+        if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+        NFCS_HIP(hipDeviceSynchronize());  // the object must be idle; this makes it so
+        if (x->state_bytes) NFCS_HIP(hipMemset(x->d_blob + x->state_off, 0, x->state_bytes));
+        NFCS_HIP(hipDeviceSynchronize());
+    }
+    std::fill(x->h.head.begin(), x->h.head.end(), 0u);
+    std::fill(x->h.last.begin(), x->h.last.end(), (uint8_t)0);
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_txq_info(const nfcs_txq* x, uint32_t* ports, uint32_t* keys, uint64_t* ring_slots) {
+    if (!x) return NFCS_EINVAL;
+    if (ports) *ports = x->t.ports;
+    if (keys) *keys = x->t.keys;
+    if (ring_slots) *ring_slots = x->t.ring_slots;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_txq_state_host(const nfcs_txq* x, uint32_t* head, uint8_t* last) {
+    if (!x) return NFCS_EINVAL;
+    if (head && x->t.keys) memcpy(head, x->h.head.data(), (size_t)x->t.keys * 4u);
+    if (last && x->t.ports) memcpy(last, x->h.last.data(), x->t.ports);
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_txq_state_device(nfcs_txq* x, uint32_t* head, uint8_t* last, void* stream) {
+    if (!x || !x->ctx) return NFCS_EINVAL;
+    DeviceGuard dg_(x->device);
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    NFCS_HIP(hipStreamSynchronize(pick(x->ctx, stream)));
+    if (head && x->t.keys) NFCS_HIP(hipMemcpy(head, x->dev.head, (size_t)x->t.keys * 4u, hipMemcpyDeviceToHost));
+    if (last && x->t.ports) {
+        std::vector<uint32_t> w;
+        try {
+            w.resize(x->t.ports);
+        } catch (...) {
+            return NFCS_ENOMEM;
+        }
+        NFCS_HIP(hipMemcpy(w.data(), x->dev.last, (size_t)x->t.ports * 4u, hipMemcpyDeviceToHost));
+        for (uint32_t p = 0; p < x->t.ports; ++p) last[p] = (uint8_t)w[p];
+    }
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_txq_append_host(nfcs_txq* x, const uint32_t* order, const uint32_t* key_start, const uint32_t* depth,
+                                  const uint64_t* handle, const nfcs_desc* desc, uint32_t n) {
+    if (!x) return NFCS_EINVAL;
+    if (n == 0) return NFCS_OK;
+    if (!handle && !desc) return NFCS_EINVAL;
+    if (!order || !key_start || (x->t.keys > 0 && !depth)) return NFCS_EINVAL;
+    nfcs::txq_append(x->t, x->h, order, key_start, depth, handle, desc, n);
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_txq_append_device(nfcs_ctx* c, nfcs_txq* x, const uint32_t* d_order, const uint32_t* d_key_start,
+                                    const uint32_t* d_depth, const uint64_t* d_handle, const nfcs_desc* d_desc, uint32_t n,
+                                    void* stream) {
+    if (!c || !x || x->ctx != c) return NFCS_EINVAL;
+    DeviceGuard dg_(c->di.device);
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    if (n == 0) return NFCS_OK;
+    if (!d_handle && !d_desc) return NFCS_EINVAL;
+    if (!d_order || !d_key_start || (x->dev.keys > 0 && !d_depth)) return NFCS_EINVAL;
+    if (((uintptr_t)d_order & 3u) || ((uintptr_t)d_key_start & 3u) || ((uintptr_t)d_depth & 3u) ||
+        ((uintptr_t)d_handle & 7u) || ((uintptr_t)d_desc & 7u))
+        return NFCS_EINVAL;
+    NFCS_HIP(nfcs::launch_txq_append(x->dev, d_order, d_key_start, d_depth, d_handle, d_desc, n, pick(c, stream)));
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_txq_dequeue_host(nfcs_txq* x, const uint32_t* budget, uint32_t budget_all, uint32_t* depth, uint64_t* tx,
+                                   uint32_t tx_cap, uint8_t* tx_queue, uint32_t* tx_start, uint32_t* dequeued) {
+    if (!x || !tx_start || (x->t.keys > 0 && !depth) || (tx_cap > 0 && !tx)) return NFCS_EINVAL;
+    nfcs::txq_dequeue_walk(x->t, x->h, budget, budget_all, depth, tx, tx_cap, tx_queue, tx_start, dequeued);
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_txq_dequeue_device(nfcs_ctx* c, nfcs_txq* x, const uint32_t* d_budget, uint32_t budget_all,
+                                     uint32_t* d_depth, uint64_t* d_tx, uint32_t tx_cap, uint8_t* d_tx_queue,
+                                     uint32_t* d_tx_start, uint32_t* d_dequeued, void* stream) {
+    if (!c || !x || x->ctx != c) return NFCS_EINVAL;
+    DeviceGuard dg_(c->di.device);
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    if (!d_tx_start || (x->dev.keys > 0 && !d_depth) || (tx_cap > 0 && !d_tx)) return NFCS_EINVAL;
+    if (((uintptr_t)d_budget & 3u) || ((uintptr_t)d_depth & 3u) || ((uintptr_t)d_tx & 7u) || ((uintptr_t)d_tx_start & 3u) ||
+        ((uintptr_t)d_dequeued & 3u))
+        return NFCS_EINVAL;
+    NFCS_HIP(nfcs::launch_txq_dequeue(x->dev, d_budget, budget_all, d_depth, d_tx, tx_cap, d_tx_queue, d_tx_start,
+                                      d_dequeued, pick(c, stream)));
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_txq_closed_form_host(uint32_t sched, uint32_t num_queues, uint32_t last, const uint32_t* depth,
+                                       uint32_t budget, uint32_t* take, uint32_t* new_last, uint8_t* seq,
+                                       uint32_t seq_cap) {
+    if (sched > NFCS_SCHED_DRR || num_queues == 0 || num_queues > NFCS_QOS_MAX_QUEUES || last >= num_queues || !depth ||
+        !take || !new_last)
+        return NFCS_EINVAL;
+    const nfcs::TxqPort pr{num_queues, 0xFFFFFFFFu, sched, 0u};
+    uint32_t d8[nfcs::kTxqQ] = {0}, D[nfcs::kTxqQ], tk[nfcs::kTxqQ];
+    for (uint32_t q = 0; q < num_queues; ++q) d8[q] = depth[q];
+    const uint64_t sum = nfcs::txq_depths(pr, d8, D);
+    const uint32_t G = (uint32_t)(sum < budget ? sum : budget);
+    nfcs::txq_take(pr, last, D, G, tk, new_last);
+    for (uint32_t q = 0; q < num_queues; ++q) {
+        take[q] = tk[q];
+        for (uint32_t r = 0; seq && r < tk[q]; ++r) {
+            const uint64_t rank = nfcs::txq_rank(pr, last, D, q, r);
+            if (rank < seq_cap) seq[rank] = (uint8_t)q;
+        }
+    }
+    return NFCS_OK;
+}
+
 NFCS_API int nfcs_update_host(nfcs_ctx* c, uint8_t* h_arena, uint64_t arena_bytes,
                               const nfcs_desc* h_desc, uint32_t n, uint8_t* h_status,
                               uint32_t flags) {

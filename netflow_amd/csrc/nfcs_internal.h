@@ -10,6 +10,7 @@
 #include "nfcs_egress.h"
 #include "nfcs_fdb.h"
 #include "nfcs_fib.h"
+#include "nfcs_txq.h"
 
 namespace nfcs {
 
@@ -254,6 +255,30 @@ inline uint64_t egress_scratch_words(uint32_t n, uint32_t keys) {
 hipError_t launch_egress_enqueue(const DevInfo& di, const EgressDev& eg, const uint32_t* port, const uint8_t* queue,
                                  uint32_t n, uint32_t* depth, uint8_t* result, uint32_t* order, uint32_t* key_start,
                                  uint32_t* key_dropped, uint32_t* scratch, hipStream_t stream);
+
+// The device copy of a TX queue object (nfcs_txq_create): the tables of TxqTables, the state
+// of TxqState (last as one word per port) and the dequeue's scratch, all sized at creation.
+struct TxqDev {
+    const uint4* port = nullptr;          // ports 16-byte records {queues, max_depth, sched, 0}
+    const uint64_t* ring_base = nullptr;  // keys + 1
+    uint64_t* ring = nullptr;             // ring_slots handles
+    uint32_t* head = nullptr;             // keys
+    uint32_t* last = nullptr;             // ports
+    uint32_t* take = nullptr;             // scratch, keys: what this dequeue takes from each key
+    uint32_t* elem_start = nullptr;       // scratch, keys + 1: the exclusive prefix of take in key order
+    uint32_t* tx_start = nullptr;         // scratch, ports + 1: each port's segment in d_tx
+    uint32_t* new_last = nullptr;         // scratch, ports
+    uint32_t ports = 0, keys = 0;
+    uint64_t ring_slots = 0;
+};
+constexpr uint32_t kTxqPlanThreads = NFCS_L2_MAX_PORTS;  // one lane per port, one workgroup
+static_assert(kTxqPlanThreads == 1024u, "the plan is one workgroup of 16 waves");
+
+hipError_t launch_txq_append(const TxqDev& t, const uint32_t* order, const uint32_t* key_start, const uint32_t* depth,
+                             const uint64_t* handle, const nfcs_desc* desc, uint32_t n, hipStream_t stream);
+hipError_t launch_txq_dequeue(const TxqDev& t, const uint32_t* budget, uint32_t budget_all, uint32_t* depth,
+                              uint64_t* tx, uint32_t tx_cap, uint8_t* tx_queue, uint32_t* tx_start, uint32_t* dequeued,
+                              hipStream_t stream);
 
 // Flood replication. Tiles of kFloodTile consecutive packets, one 1,024-thread workgroup
 // each, one lane per packet. Scratch: one FloodSum per tile (the count kernel's sums, which the scan turns

@@ -3359,4 +3359,199 @@ hipError_t launch_digest(const DevInfo& di, const uint8_t* arena, uint64_t arena
     return hipGetLastError();
 }
 
+// ---- TX queues: append, and the dequeue as plan / gather / commit ---------------------
+// Every loop bound below is a launch parameter (`trips`) or a constant of at most 10; no atomics, no
+// inline assembly, plain vector loads and stores.
+
+DEV TxqPort txq_port(const TxqDev& t, uint32_t p) {
+    const uint4 r = t.port[p];
+    return TxqPort{r.x, r.y, r.z, r.w};
+}
+
+// The key whose range of `start` (keys + 1 ascending words, start[0] = 0) holds e: the last k with
+// start[k] <= e, by an upper-bound search of `trips` >= bit_length(keys + 1) steps, so empty keys (equal
+// neighbours) are stepped over. e >= start[keys] gives keys; the callers guard k < keys.
+DEV uint32_t txq_find_key(const uint32_t* __restrict__ start, uint32_t keys, uint32_t trips, uint32_t e) {
+    uint32_t lo = 0, hi = keys + 1u;  // the first index in [0, keys] with start[index] > e, or keys + 1
+    for (uint32_t s = 0; s < trips; ++s) {
+        if (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (start[mid] > e) hi = mid;
+            else lo = mid + 1u;
+        }
+    }
+    return lo - 1u;
+}
+
+// One lane per enqueued position j < key_start[keys]; the grid covers n. Consecutive lanes of one key
+// store consecutive ring slots (up to the wrap); the handle is gathered at order[j].
+__global__ __launch_bounds__(kBlock) void txq_append_kernel(const TxqDev t, const uint32_t* __restrict__ order,
+                                                            const uint32_t* __restrict__ key_start,
+                                                            const uint32_t* __restrict__ depth,
+                                                            const uint64_t* __restrict__ handle,
+                                                            const nfcs_desc* __restrict__ desc, uint32_t n,
+                                                            uint32_t trips) {
+    const uint64_t j64 = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j64 >= n) return;
+    const uint32_t j = (uint32_t)j64, keys = t.keys;
+    if (j >= key_start[keys]) return;
+    const uint32_t k = txq_find_key(key_start, keys, trips, j);
+    if (k >= keys) return;
+    const uint32_t b = key_start[k], e = key_start[k + 1u];
+    if (j < b || j >= e || e > n) return;
+    const uint32_t cnt = e - b, d = depth[k];
+    const TxqPort pr = txq_port(t, k / kTxqQ);
+    const uint32_t cap = txq_cap(pr, k % kTxqQ), head = t.head[k];
+    if (cap == 0u || d < cnt || d > cap || head >= cap) return;  // inconsistent input: nothing for this key
+    const uint32_t i = order[j];
+    if (i >= n) return;
+    uint64_t pos = (uint64_t)head + (d - cnt) + (j - b);  // below 2 * cap
+    if (pos >= cap) pos -= cap;
+    const uint64_t slot = t.ring_base[k] + pos;
+    if (pos >= cap || slot >= t.ring_slots) return;
+    uint64_t h;
+    if (handle) {
+        h = handle[i];
+    } else {
+        const uint2 dl = ((const uint2*)desc)[i];
+        h = txq_desc_handle(dl.x, dl.y);
+    }
+    t.ring[slot] = h;
+}
+
+hipError_t launch_txq_append(const TxqDev& t, const uint32_t* order, const uint32_t* key_start, const uint32_t* depth,
+                             const uint64_t* handle, const nfcs_desc* desc, uint32_t n, hipStream_t stream) {
+    if (n == 0 || t.keys == 0) return hipSuccess;
+    const uint32_t trips = 32u - (uint32_t)__builtin_clz(t.keys + 1u);
+    hipLaunchKernelGGL(txq_append_kernel, dim3((n + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, t, order, key_start,
+                       depth, handle, desc, n, trips);
+    return hipGetLastError();
+}
+
+// The plan: one workgroup, one lane per port. want = min(budget, sum D), W = its exclusive prefix over the
+// ports in 64 bits (an LDS scan), G by the tx_cap rule, take[q] by txq_take.
+__global__ __launch_bounds__(kTxqPlanThreads) void txq_plan_kernel(const TxqDev t, const uint32_t* __restrict__ budget,
+                                                                   uint32_t budget_all,
+                                                                   const uint32_t* __restrict__ depth, uint32_t tx_cap,
+                                                                   uint32_t* __restrict__ tx_start_out) {
+    __shared__ uint64_t scan[kTxqPlanThreads];
+    const uint32_t p = threadIdx.x;
+    const bool live = p < t.ports;
+    TxqPort pr{0u, 0u, 0u, 0u};
+    uint32_t D[kTxqQ] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    uint32_t want = 0;
+    if (live) {
+        pr = txq_port(t, p);
+        uint32_t d8[kTxqQ];
+        for (uint32_t q = 0; q < kTxqQ; ++q) d8[q] = depth[p * kTxqQ + q];
+        const uint64_t sum = txq_depths(pr, d8, D);
+        const uint32_t b = budget ? budget[p] : budget_all;
+        want = (uint32_t)(sum < b ? sum : b);
+    }
+    scan[p] = want;
+    __syncthreads();
+    for (uint32_t off = 1; off < kTxqPlanThreads; off <<= 1) {  // inclusive scan, 10 steps
+        const uint64_t v = p >= off ? scan[p - off] : 0ull;
+        __syncthreads();
+        scan[p] += v;
+        __syncthreads();
+    }
+    const uint64_t incl = scan[p];
+    if (t.ports == 0u) {
+        if (p == 0u) {
+            t.tx_start[0] = 0u;
+            tx_start_out[0] = 0u;
+            t.elem_start[0] = 0u;
+        }
+        return;
+    }
+    if (!live) return;
+    uint32_t start, take[kTxqQ], new_last;
+    const uint32_t last = t.last[p];
+    const uint32_t G = txq_grant(incl - want, want, tx_cap, &start);
+    txq_take(pr, last, D, G, take, &new_last);
+    t.tx_start[p] = start;
+    tx_start_out[p] = start;
+    t.new_last[p] = new_last;
+    uint32_t run = start;
+    for (uint32_t q = 0; q < kTxqQ; ++q) {
+        t.take[p * kTxqQ + q] = take[q];
+        t.elem_start[p * kTxqQ + q] = run;
+        run += take[q];
+    }
+    if (p == t.ports - 1u) {
+        const uint32_t total = (uint32_t)(incl < tx_cap ? incl : tx_cap);
+        t.tx_start[t.ports] = total;
+        tx_start_out[t.ports] = total;
+        t.elem_start[t.keys] = total;
+    }
+}
+
+// The gather: one lane per dequeued element e < tx_start[ports], in key order, so consecutive lanes read
+// consecutive ring slots; each stores its handle at its TX rank within the port's segment.
+__global__ __launch_bounds__(kBlock) void txq_gather_kernel(const TxqDev t, const uint32_t* __restrict__ depth,
+                                                            uint64_t* __restrict__ tx, uint32_t tx_cap,
+                                                            uint8_t* __restrict__ tx_queue, uint32_t trips) {
+    const uint64_t e64 = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t keys = t.keys;
+    if (e64 >= tx_cap || e64 >= t.elem_start[keys]) return;
+    const uint32_t e = (uint32_t)e64;
+    const uint32_t k = txq_find_key(t.elem_start, keys, trips, e);
+    if (k >= keys) return;
+    const uint32_t r = e - t.elem_start[k];
+    if (r >= t.take[k]) return;
+    const uint32_t p = k / kTxqQ, q = k % kTxqQ;
+    const TxqPort pr = txq_port(t, p);
+    uint32_t d8[kTxqQ], D[kTxqQ];
+    for (uint32_t o = 0; o < kTxqQ; ++o) d8[o] = depth[p * kTxqQ + o];
+    txq_depths(pr, d8, D);
+    const uint32_t cap = txq_cap(pr, q), head = t.head[k];
+    if (cap == 0u || head >= cap || r >= cap) return;
+    uint64_t pos = (uint64_t)head + r;  // below 2 * cap
+    if (pos >= cap) pos -= cap;
+    const uint64_t slot = t.ring_base[k] + pos;
+    if (slot >= t.ring_slots) return;
+    const uint64_t h = t.ring[slot];
+    const uint64_t rank = txq_rank(pr, t.last[p], D, q, r);
+    const uint32_t seg = t.tx_start[p], seg_end = t.tx_start[p + 1u];
+    const uint64_t dst = seg + rank;
+    if (dst >= seg_end || dst >= tx_cap) return;
+    tx[dst] = h;
+    if (tx_queue) tx_queue[dst] = (uint8_t)q;
+}
+
+// The commit: one lane per key, after the gather (which reads the old heads, depths and last).
+__global__ __launch_bounds__(kBlock) void txq_commit_kernel(const TxqDev t, uint32_t* __restrict__ depth,
+                                                            uint32_t* __restrict__ dequeued) {
+    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= t.keys) return;
+    const uint32_t tk = t.take[k];
+    if (dequeued) dequeued[k] = tk;
+    if (k % kTxqQ == 0u) t.last[k / kTxqQ] = t.new_last[k / kTxqQ];
+    if (tk == 0u) return;
+    const uint32_t cap = txq_cap(txq_port(t, k / kTxqQ), k % kTxqQ);
+    if (cap == 0u) return;
+    depth[k] -= tk;  // tk <= min(depth, cap)
+    uint64_t h = (uint64_t)t.head[k] + tk;
+    if (h >= cap) h -= cap;
+    t.head[k] = (uint32_t)h;
+}
+
+hipError_t launch_txq_dequeue(const TxqDev& t, const uint32_t* budget, uint32_t budget_all, uint32_t* depth,
+                              uint64_t* tx, uint32_t tx_cap, uint8_t* tx_queue, uint32_t* tx_start, uint32_t* dequeued,
+                              hipStream_t stream) {
+    hipLaunchKernelGGL(txq_plan_kernel, dim3(1), dim3(kTxqPlanThreads), 0, stream, t, budget, budget_all, depth, tx_cap,
+                       tx_start);
+    const uint64_t most = t.ring_slots < tx_cap ? t.ring_slots : tx_cap;
+    if (most > 0 && t.keys > 0) {
+        const uint32_t trips = 32u - (uint32_t)__builtin_clz(t.keys + 1u);
+        hipLaunchKernelGGL(txq_gather_kernel, dim3((uint32_t)((most + kBlock - 1u) / kBlock)), dim3(kBlock), 0, stream, t,
+                           depth, tx, tx_cap, tx_queue, trips);
+    }
+    if (t.keys > 0)
+        hipLaunchKernelGGL(txq_commit_kernel, dim3((t.keys + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, t, depth,
+                           dequeued);
+    return hipGetLastError();
+}
+
 }  // namespace nfcs

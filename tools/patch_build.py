@@ -1,6 +1,6 @@
 """patch_build.py — measurement tool (not product): builds libnfcs.so from the product sources with
 literal text substitutions in the sources under netflow_amd/csrc (nfcs_kernels.hip, nfcs_api.hip,
-nfcs_internal.h, nfcs_fib.h, nfcs_acl.h, nfcs_fdb.h, nfcs_egress.h; each OLD must occur exactly COUNT times over them, default 1; the patched copies are
+nfcs_internal.h, nfcs_fib.h, nfcs_acl.h, nfcs_fdb.h, nfcs_egress.h, nfcs_txq.h; each OLD must occur exactly COUNT times over them, default 1; the patched copies are
 compiled together from one scratch directory, so a quoted #include finds the patched header),
 so a one-line policy or shape change can be A/B-timed against the product without touching it:
   python tools/patch_build.py OUT.so 'OLD' 'NEW' ['OLD' 'NEW' ...]
@@ -19,7 +19,7 @@ def main():
     if not pairs or len(pairs) % 2:
         raise SystemExit(__doc__)
     csrc = os.path.join(ROOT, "netflow_amd", "csrc")
-    names = ("nfcs_kernels.hip", "nfcs_api.hip", "nfcs_internal.h", "nfcs_fib.h", "nfcs_acl.h", "nfcs_fdb.h", "nfcs_egress.h")
+    names = ("nfcs_kernels.hip", "nfcs_api.hip", "nfcs_internal.h", "nfcs_fib.h", "nfcs_acl.h", "nfcs_fdb.h", "nfcs_egress.h", "nfcs_txq.h")
     srcs = {f: open(os.path.join(csrc, f)).read() for f in names}
     for old, new in zip(pairs[::2], pairs[1::2]):
         cnt = 1
