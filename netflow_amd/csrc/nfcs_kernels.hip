@@ -270,11 +270,12 @@ struct RPlan {
     uint32_t ipw;    // ip_off | ip_val << 16
     uint32_t rs, re, fs;
     uint32_t corr;   // pseudo-header words minus over-counted bytes (two's complement)
+    uint32_t old;    // fast path: the frame's IPv4 field bytes as read (LE16) | its L4 field bytes << 16
 };
 
 DEV RPlan rplan_none(uint32_t st) {
     RPlan P;
-    P.st = st; P.flags = 0; P.ipw = 0; P.rs = 0; P.re = 0; P.fs = 0; P.corr = 0;
+    P.st = st; P.flags = 0; P.ipw = 0; P.rs = 0; P.re = 0; P.fs = 0; P.corr = 0; P.old = 0;
     return P;
 }
 
@@ -293,7 +294,9 @@ DEV uint4 strip_tag(const uint4& c, bool tagged) {
 
 // L4 branch of packet.hpp:773-889 in view coordinates with compile-time l2 = 14 and l4
 // (34 for IPv4 with IHL 5, 54 for IPv6); sh = 4 for tagged frames shifts the frame offsets.
-template <int R>
+// OLD (here and in the two plans below): also return the checksum fields' bytes as they are (RPlan::old);
+// the fused forward does not ask for them and compiles as before.
+template <int R, bool OLD>
 DEV RPlan fast_l4(const RowHdr<R>& V, RPlan P, uint32_t lenv, uint32_t v4, uint32_t l4, uint32_t proto,
                   uint32_t sh) {
     const uint32_t l2 = 14, ihl4 = 20;
@@ -349,6 +352,7 @@ DEV RPlan fast_l4(const RowHdr<R>& V, RPlan P, uint32_t lenv, uint32_t v4, uint3
     if (fs + 1 < re) sub += V.b(fs + 1) << (((fs + 1 + sh) & 1u) ? 8 : 0);
     const uint32_t t = re - 1;
     if ((L & 1u) && !(t >= fs && t < fs + 2)) fl |= F_TAIL;
+    if (OLD) P.old |= (V.b(fs) | (V.b(fs + 1) << 8)) << 16;  // both in the frame: fs + 2 <= lenv in every branch
     P.st = st;
     P.flags |= fl;
     P.rs = l4 + sh;
@@ -364,7 +368,7 @@ DEV RPlan fast_l4(const RowHdr<R>& V, RPlan P, uint32_t lenv, uint32_t v4, uint3
 // pass instead of one per protocol, and the checksum field's bytes are read at their constant offsets
 // instead of through two runtime-indexed ds_bpermute round trips. Same conditions and values as
 // fast_l4 (packet.hpp:773-889).
-template <int R>
+template <int R, bool OLD>
 DEV RPlan fast_l4_v4(const RowHdr<R>& V, RPlan P, uint32_t lenv, uint32_t proto, uint32_t sh) {
     const bool isT = proto == 6, isU = proto == 17, isI = proto == 1;
     const uint32_t d4 = V.dw(4), d6 = V.dw(6), d7 = V.dw(7), d8 = V.dw(8);
@@ -396,12 +400,14 @@ DEV RPlan fast_l4_v4(const RowHdr<R>& V, RPlan P, uint32_t lenv, uint32_t proto,
     P.re = ok ? re + sh : P.re;
     P.fs = ok ? fs + sh : P.fs;
     P.corr = ok ? add - sub : P.corr;
+    // the field's two bytes as they are (TCP: 49-50, bits 8-23 of dword 12; UDP 40-41; ICMP 36-37)
+    if (OLD) P.old |= (isT ? (d12 >> 8) : (isU ? d10 : d9)) << 16;
     return P;
 }
 
 // Common headers with compile-time offsets: untagged / 802.1Q; IPv4 with IHL 5; IPv6; non-IP.
 // Returns F_SEQ in flags for everything else (IHL != 5: options, IHL < 5, past the frame).
-template <int R>
+template <int R, bool OLD>
 DEV RPlan fast_plan(const uint4& c0, uint32_t rowbase4, uint32_t len) {
     const RowHdr<R> h{c0, rowbase4};
     const bool tagged = (len >= 14) && h.be16(12) == 0x8100u;  // ethernet(): l2 = 18
@@ -418,13 +424,14 @@ DEV RPlan fast_plan(const uint4& c0, uint32_t rowbase4, uint32_t len) {
         RPlan P = rplan_none(NFCS_ST_V4);
         P.flags = F_IP;
         P.ipw = (24u + sh) | (((~fold32(s)) & 0xFFFFu) << 16);
-        return fast_l4_v4(V, P, lenv, V.b(23), sh);
+        if (OLD) P.old = V.le16(24);
+        return fast_l4_v4<R, OLD>(V, P, lenv, V.b(23), sh);
     }
     // 741-765: effective EtherType (after one tag) must be IPv6 and the nibble 6
     const uint32_t et = (len >= 14 + sh) ? V.be16(12) : 0u;
     if (et != 0x86DDu || !(len >= 14 + sh && lenv >= 54 && (b0 >> 4) == 6))
         return rplan_none(NFCS_ST_NONE);
-    return fast_l4(V, rplan_none(NFCS_ST_V6), lenv, 0u, 54u, V.b(20), sh);
+    return fast_l4<R, OLD>(V, rplan_none(NFCS_ST_V6), lenv, 0u, 54u, V.b(20), sh);
 }
 
 // Any header, parsed by one lane from global memory (IP options, IHL < 5, past the frame).
@@ -823,6 +830,9 @@ DEV void row_stage(RowStage<K>& S, uint8_t* arena, uint64_t arena_bytes, const n
 //               evicted from the memory-side cache into, the read stream); other waves as SF_INLINE;
 //   SF_RECORDS  patch records only, frames untouched (nfcs_update_host: only the records cross
 //               PCIe back).
+// In the plain update's fast path a field whose bytes already equal the computed value is not stored
+// (SF_INLINE) and is recorded as "none" in the engine's own workspace (SF_DEFER, so the write pass issues
+// nothing for it); a caller's records (SF_RECORDS, SF_DEFER into d_patch) hold every field (row_process).
 // Round 4 measured, under rotating batches, forms storing each frame's first 64 bytes whole (from
 // the read pass, or from 64-byte records through a write pass) and write passes of write-back /
 // write-through stores: all slower than SF_DEFER's masked `nt` stores (their code is
@@ -870,7 +880,7 @@ DEV uint4 hdr_view(const RowStage<K>& S, uint32_t rowbase4, uint32_t rl) {
 // builds against the round-4 sources, git 00f5686.)
 template <int K, int R = 16, bool FWD = false, bool NT = false, bool DFR = false, bool LA = false>
 DEV void row_process(const RowStage<K>& S, uint32_t rl, uint32_t rowbase4, uint8_t* status,
-                     nfcs_patch* rec, bool frame_stores, uint32_t table_n = 0,
+                     nfcs_patch* rec, bool rec_full, bool frame_stores, uint32_t table_n = 0,
                      const uint32_t* wmac = nullptr, const nfcs_nexthop* table = nullptr) {
     const uint32_t len = S.len;
     uint8_t* frame = S.frame;
@@ -915,7 +925,7 @@ DEV void row_process(const RowStage<K>& S, uint32_t rl, uint32_t rowbase4, uint8
             else h0.y -= 1u << 16;
         }
     }
-    RPlan P = fast_plan<R>(h0, rowbase4, len);
+    RPlan P = fast_plan<R, !FWD>(h0, rowbase4, len);
     const bool act = live && (!FWD || fwd);  // rows whose checksums are updated
     // uncommon headers (IP options, IHL < 5, IHL past the frame) take the cold path below,
     // after the chunk registers are dead, so it adds nothing to the kernel's register peak
@@ -1001,6 +1011,15 @@ DEV void row_process(const RowStage<K>& S, uint32_t rl, uint32_t rowbase4, uint8
         if ((P.flags & F_UDP) && c == 0) c = 0xFFFFu;  // 867-871
         l4w = P.fs | (c << 16);
     }
+    // Store skipping (the plain update's fast path): a field whose two bytes in the frame already equal
+    // the computed value is not written — memory is the same either way, and received traffic or an
+    // L2-only edit leaves most fields so. The plan read the old bytes with the header (P.old, in the
+    // same view), so the comparison is two VALU instructions per field and exact: 0x0000 and 0xFFFF
+    // differ. sipw / sl4w are what the frame still needs (an unchanged field becomes "none"): the inline
+    // stores and the engine's own deferred records follow these; a caller's records keep every field.
+    const bool ip_new = FWD || (P.old & 0xFFFFu) != (ipw >> 16), l4_new = FWD || (P.old >> 16) != (l4w >> 16);
+    const uint32_t sipw = ip_new ? ipw : (uint32_t)NFCS_PATCH_NONE;
+    const uint32_t sl4w = l4_new ? l4w : (uint32_t)NFCS_PATCH_NONE;
     // The (at most 4) checksum bytes from lanes 0..3 of the row, write-through (sc1: the L2
     // keeps no dirty copy of the header line; session 3, C1 +2.5% / C3 +5% over write-back
     // stores; byte stores measured fastest against chunk, dword, whole-line and re-load-then-
@@ -1008,9 +1027,11 @@ DEV void row_process(const RowStage<K>& S, uint32_t rl, uint32_t rowbase4, uint8
     // session 3, C3 +2%, uniform 1024-byte frames +2.7%; in the long shape it cost 64K-packet
     // bursts of 9000-byte frames 3%, in 8-lane rows IMIX ±1%), then the status byte / patch
     // record from lane 0.
-    auto emit = [&](bool on, uint32_t st_, uint32_t ipw_, uint32_t l4w_, bool stores, bool recw = true) {
+    // ipw_ / l4w_: the fields as computed; sip_ / sl4_: those of them the frame still needs
+    auto emit = [&](bool on, uint32_t st_, uint32_t ipw_, uint32_t l4w_, uint32_t sip_, uint32_t sl4_, bool stores,
+                    bool recw = true) {
         if (stores && on && rl < 4) {
-            const uint32_t w = (rl & 2u) ? l4w_ : ipw_;
+            const uint32_t w = (rl & 2u) ? sl4_ : sip_;
             const uint32_t pos = (w & 0xFFFFu) + (rl & 1u);
             if ((w & 0xFFFFu) != NFCS_PATCH_NONE) {
                 if (NT) st8_nt(frame + pos, w >> (16 + 8 * (rl & 1u)));
@@ -1020,9 +1041,10 @@ DEV void row_process(const RowStage<K>& S, uint32_t rl, uint32_t rowbase4, uint8
         if (on && rl == 0) {
             if (status) status[S.p] = (uint8_t)st_;
             if (rec && recw) {
+                const uint32_t ri = rec_full ? ipw_ : sip_, rl4 = rec_full ? l4w_ : sl4_;
                 uint2 r;
-                r.x = (ipw_ & 0xFFFFu) | (l4w_ << 16);
-                r.y = (ipw_ >> 16) | (l4w_ & 0xFFFF0000u);
+                r.x = (ri & 0xFFFFu) | (rl4 << 16);
+                r.y = (ri >> 16) | (rl4 & 0xFFFF0000u);
                 ((uint2*)rec)[S.p] = r;
             }
         }
@@ -1053,11 +1075,11 @@ DEV void row_process(const RowStage<K>& S, uint32_t rl, uint32_t rowbase4, uint8
         // a deferred wave (large bursts, SF_DEFER) leaves the frame alone here: its forward record
         // (fwd_record) goes to apply_fwd_kernel, which writes the rewritten bytes without reading
         // the frame again
-        emit(S.valid && !slow, st, ipw, l4w, false, !DFR);
+        emit(S.valid && !slow, st, ipw, l4w, ipw, l4w, false, !DFR);
         if (DFR && rec && S.valid && !slow && rl == 0)
             ((uint2*)rec)[S.p] = (fwd && live) ? fwd_record(ipw, l4w, ttl - 1u, proto, tagged) : make_uint2(0xFFFFFFFFu, 0u);
     } else {
-        emit(S.valid && !slow, st, ipw, l4w, frame_stores);
+        emit(S.valid && !slow, st, ipw, l4w, sipw, sl4w, frame_stores);
     }
     if (__builtin_amdgcn_ballot_w64(slow) != 0) {  // cold path, wave-uniform branch
         // Uncommon headers, handled last so that only the frame address and length are live
@@ -1127,7 +1149,7 @@ DEV void row_process(const RowStage<K>& S, uint32_t rl, uint32_t rowbase4, uint8
         }
         if (FWD) st2 |= NFCS_ST_FLAG_FWD;
         // the forward always stores (its header rewrite went out above)
-        emit(slow, st2, ipw2, l4w2, !seq && (FWD || frame_stores), !(FWD && DFR));
+        emit(slow, st2, ipw2, l4w2, ipw2, l4w2, !seq && (FWD || frame_stores), !(FWD && DFR));
         // the forward stored everything of an uncommon header here: nothing left for the write pass
         if (FWD && DFR && rec && slow && rl == 0) ((uint2*)rec)[S.p] = make_uint2(0xFFFFFFFFu, 0u);
     }
@@ -1182,7 +1204,8 @@ DEV void rows_body(const DescW<PW>& D, uint64_t pw, uint32_t n, uint8_t* arena, 
     // inline checksum stores past the caches in the short-frame shape (16-lane rows, frame-relative
     // windows), write-through elsewhere (see row_process)
     row_process<K, R, FWD, !FWD && R == 16 && !LA, FWD && SF == SF_DEFER, LA>(S, rl, rowbase4, status, rec,
-                                                                                 frame_stores, table_n, wmac, table);
+                                                                                 patch != nullptr, frame_stores, table_n,
+                                                                                 wmac, table);
 }
 
 // One wave of update_rows_kernel: its PW packets from the descriptor load on.
@@ -1751,7 +1774,7 @@ __global__ __launch_bounds__(kBlock) void vlan_rows_kernel(uint8_t* __restrict__
     uint32_t carry = row_bcast<R - 1, R>(v[K - 1].w);  // push: old dword before batch 1
 
     // update_checksums() on the edited frame (690 / 718)
-    RPlan P = fast_plan<R>(rot ? vlan_view<K, R>(nv, rowbase4, rl, mis) : nv[0], rowbase4, nlen);
+    RPlan P = fast_plan<R, false>(rot ? vlan_view<K, R>(nv, rowbase4, rl, mis) : nv[0], rowbase4, nlen);
     const bool slow = act && (P.st >> 8) != 0;
     if (!act || slow) P = rplan_none(0);
     const uint32_t re = (P.flags & F_L4) ? P.re : 0u, lo4 = P.rs & ~3u;
