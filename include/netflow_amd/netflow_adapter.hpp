@@ -150,6 +150,17 @@ inline int make_acl(const std::vector<AclRuleT>& rules, nfcs_acl** out) {
     return make_acl_from(rules, out);
 }
 
+// A committed set of egress ACLs (nfcs_aclset, for nfcs_egress_acl_device) from the switch's named ACLs and
+// its bindings: lists[name] = AclManager::get_all_rules(name), port_to_name = (port,
+// *InterfaceManager::get_applied_acl_name(port, AclDirection::EGRESS)) for every port that has a name. A bound
+// name without a list (a deleted ACL) permits, as AclManager::evaluate does. The work is
+// netflow_amd::make_acl_set_from (packet.hpp).
+template <class AclRuleT = netflow::AclRule>
+inline int make_acl_set(const std::map<std::string, std::vector<AclRuleT>>& lists,
+                        const std::vector<std::pair<uint32_t, std::string>>& port_to_name, nfcs_aclset** out) {
+    return make_acl_set_from(lists, port_to_name, out);
+}
+
 inline int l2_lookup_batch(netflow::Packet* const* pkts, size_t n, const nfcs_fdb* fdb, uint32_t ingress_port,
                            uint32_t* egress_port, uint8_t* verdict = nullptr, uint16_t* vlan = nullptr,
                            uint8_t* learn = nullptr, const uint8_t* rt_verdict = nullptr) {

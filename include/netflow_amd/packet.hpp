@@ -35,7 +35,9 @@
 //   netflow_amd::txq_append_batch(nfcs_txq*, order, key_start, depth, handle, n)
 //   netflow_amd::txq_dequeue_batch(nfcs_txq*, budget, budget_all, depth, tx, tx_cap, tx_queue, tx_start, ...)
 // (nfcs_txq_append_device / nfcs_txq_dequeue_device: rings that persist across bursts, drained per port in
-// the reference's dequeue order).
+// the reference's dequeue order). The egress ACLs between the VLAN edit and the enqueue (one rule list per
+// egress port, chosen per packet) run through the C ABI on device arrays (nfcs_egress_acl_device); their
+// nfcs_aclset comes from make_acl_set_from (named rule vectors + (port, applied name) pairs).
 //
 // The batch entry points are templates over the packet type: they take this header's Packet or
 // the reference's own netflow::Packet (include/netflow_amd/netflow_adapter.hpp), whose buffers
@@ -51,6 +53,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -1203,9 +1206,7 @@ inline int route_lookup_batch(Packet* const* pkts, size_t n, const nfcs_fib* fib
 // engaged optional sets the field's bit; the address masks are full, which is the reference's exact
 // match. *out: the list (nfcs_acl_destroy it), or nullptr on error.
 template <class Rule>
-inline int make_acl_from(const std::vector<Rule>& rules, nfcs_acl** out) {
-    if (!out) return NFCS_EINVAL;
-    *out = nullptr;
+inline std::vector<nfcs_acl_rule> acl_records_from(const std::vector<Rule>& rules) {
     std::vector<nfcs_acl_rule> recs;
     recs.reserve(rules.size());
     for (const Rule& a : rules) {
@@ -1225,12 +1226,58 @@ inline int make_acl_from(const std::vector<Rule>& rules, nfcs_acl** out) {
         if (a.dst_port) { r.fields |= NFCS_ACL_F_DST_PORT; r.dst_port = *a.dst_port; }
         recs.push_back(r);
     }
+    return recs;
+}
+
+template <class Rule>
+inline int make_acl_from(const std::vector<Rule>& rules, nfcs_acl** out) {
+    if (!out) return NFCS_EINVAL;
+    *out = nullptr;
+    const std::vector<nfcs_acl_rule> recs = acl_records_from(rules);
     nfcs_acl* acl = nullptr;
     int rc = nfcs_acl_create(&acl);
     if (!rc) rc = nfcs_acl_set_rules(acl, recs.data(), static_cast<uint32_t>(recs.size()));
     if (!rc) rc = nfcs_acl_commit(acl);
     if (rc && acl) nfcs_acl_destroy(acl);
     else *out = acl;
+    return rc;
+}
+
+// A committed nfcs_aclset (the egress ACLs, one list per egress port) from the switch's named ACLs and its
+// bindings: `lists` maps a name to AclManager::get_all_rules(name) as it is (rules as make_acl_from takes
+// them), port_to_name holds (port, InterfaceManager::get_applied_acl_name(port, EGRESS)) for every bound
+// port. The names get list ids in the map's order. A bound name that `lists` does not hold binds its port to
+// a removed list, which reads as the reference's "ACL not found": PERMIT. More than NFCS_ACLSET_MAX_LISTS
+// names (absent ones included), a port at or above NFCS_L2_MAX_PORTS, or lists that pad to more than
+// NFCS_ACL_MAX_RULES rules together: NFCS_EINVAL. *out: the set (nfcs_aclset_destroy it; upload it with
+// nfcs_aclset_upload before nfcs_egress_acl_device), or nullptr on error.
+template <class Rule>
+inline int make_acl_set_from(const std::map<std::string, std::vector<Rule>>& lists,
+                             const std::vector<std::pair<uint32_t, std::string>>& port_to_name, nfcs_aclset** out) {
+    if (!out) return NFCS_EINVAL;
+    *out = nullptr;
+    nfcs_aclset* set = nullptr;
+    int rc = nfcs_aclset_create(&set);
+    std::map<std::string, uint32_t> id_of;
+    for (const auto& kv : lists) {
+        if (rc) break;
+        const uint32_t id = static_cast<uint32_t>(id_of.size());
+        id_of[kv.first] = id;
+        const std::vector<nfcs_acl_rule> recs = acl_records_from(kv.second);
+        rc = nfcs_aclset_set_list(set, id, recs.data(), static_cast<uint32_t>(recs.size()));
+    }
+    for (const auto& pn : port_to_name) {
+        if (rc) break;
+        auto it = id_of.find(pn.second);
+        if (it == id_of.end()) {  // a name without a list: an id of its own, set and removed
+            it = id_of.emplace(pn.second, static_cast<uint32_t>(id_of.size())).first;
+            rc = nfcs_aclset_remove_list(set, it->second);
+        }
+        if (!rc) rc = nfcs_aclset_bind_port(set, pn.first, it->second);
+    }
+    if (!rc) rc = nfcs_aclset_commit(set);
+    if (rc && set) nfcs_aclset_destroy(set);
+    else *out = set;
     return rc;
 }
 

@@ -466,10 +466,10 @@ NFCS_API int nfcs_acl_eval_host(const nfcs_acl* acl, const uint8_t* frame, uint3
  *               after the forward, on the egress port's rules, serves the egress ACL.
  * n == 0 returns NFCS_OK without a launch. acl must be uploaded to ctx (else NFCS_EINVAL) and stay
  * unchanged until the call completes.
- * ONE rule list per call. Choosing the list per packet (ports bound to different ACLs inside one
- * burst) is out of scope: the scan is wave-uniform, every lane reading the same rule, and a list per
- * lane would make it diverge. RX bursts arrive per port; a caller with a mixed burst groups it by
- * port first. */
+ * ONE rule list per call: RX bursts arrive per port, so this is the ingress ACL's form. The egress
+ * side, where every packet of a burst has its own egress port and with it its own list, is
+ * nfcs_egress_acl_device (the egress ACLs' section further down): it chooses the list per packet and
+ * keeps this scan wave-uniform by scanning each list present in a wave once. */
 NFCS_API int nfcs_acl_eval_device(nfcs_ctx* ctx, const nfcs_acl* acl, const uint8_t* d_arena,
                                   uint64_t arena_bytes, const nfcs_desc* d_desc, uint32_t n,
                                   uint8_t* d_action, uint32_t* d_rule, uint32_t* d_redirect,
@@ -675,8 +675,9 @@ NFCS_API int nfcs_l2_lookup_device(nfcs_ctx* ctx, const nfcs_fdb* fdb, uint32_t 
  *  - Scratch (one 24-byte record per tile of NFCS_FLOOD_TILE_PKTS packets) belongs to the context, grows on
  *    demand and is freed by nfcs_ctx_destroy; a failed allocation returns NFCS_ENOMEM and leaves the context
  *    usable, as the enqueue does.
- * STILL OUT OF SCOPE: per-port egress ACLs on the copies (as in the egress section); the ingress ACL's
- * REDIRECT path; interface TX counters. */
+ * Per-port egress ACLs on the copies: nfcs_egress_acl_device over the item list, between nfcs_vlan_device
+ * and nfcs_egress_enqueue_device (the egress ACLs' section).
+ * STILL OUT OF SCOPE: the ingress ACL's REDIRECT path; interface TX counters. */
 #define NFCS_FLOOD_TILE_PKTS 1024u /* packets per scan tile; SPEED ONLY, tests place sizes around it */
 #define NFCS_ITEM_NONE 0xFFFFFFFFu
 
@@ -760,10 +761,9 @@ NFCS_API int nfcs_vlan_device(nfcs_ctx* ctx, uint8_t* d_arena, uint64_t arena_by
  * Flooded packets: NFCS_L2_FLOOD packets have no port and read NFCS_EQ_SKIP when these calls run over the
  * burst itself; run over the item list of nfcs_flood_expand_device (the section above VLAN) they cover the
  * flood copies as well.
+ * Per-port egress ACLs over a mixed burst are nfcs_egress_acl_device (the egress ACLs' section below), run
+ * between nfcs_vlan_device and nfcs_egress_enqueue_device on the plan's d_port.
  * OUT OF SCOPE:
- *  - per-port egress ACLs over a mixed burst: nfcs_acl_eval_device takes one rule list per call. A caller
- *    with one egress list may still pass d_port as that call's d_nh to mask denied packets; that masking
- *    also drops REDIRECT, which the reference's egress path treats as PERMIT;
  *  - token buckets and rate limits: the reference's are placeholders (should_transmit's bucket is a TODO,
  *    update_token_buckets is empty). Scheduling and dequeue are the TX queues' section below, which
  *    subtracts what it dequeues from d_depth;
@@ -879,6 +879,101 @@ NFCS_API int nfcs_egress_enqueue_host(const nfcs_egress* eg, const uint32_t* por
                                       uint32_t n, uint32_t* depth, uint8_t* result, uint32_t* order,
                                       uint32_t* key_start, uint32_t* key_dropped);
 
+/* ---- Egress ACLs: one rule list per egress port, one evaluation over a mixed-port burst ---------- */
+
+/* The egress ACL of Switch::process_egress_pipeline (switch.hpp:113-139), the step between
+ * VlanManager::process_egress and QosManager::enqueue_packet:
+ *     name = get_applied_acl_name(egress_port, EGRESS); if evaluate(name, pkt) == DENY: tx stats, drop.
+ * After the lookups and the flood expansion every item of a burst has its own egress port, so the list is
+ * chosen PER PACKET from d_port[i]. An nfcs_aclset holds the rule lists (by id, 0..NFCS_ACLSET_MAX_LISTS-1)
+ * and the port -> list bindings; nfcs_egress_acl_device evaluates a burst against it in one kernel that
+ * reads every frame once. The symbols of this section were added without changing NFCS_ABI_VERSION (it stays
+ * 2): detect them by symbol lookup (dlsym "nfcs_aclset_create").
+ *
+ * The list of a port. A port that was never bound, a port bound to a list that was never set or was removed
+ * (AclManager::evaluate answers PERMIT for a name it does not know, acl_manager.cpp:162-166), a port bound to
+ * an empty list, and a port id at or above the committed `ports` all have NO LIST: NFCS_ACL_PERMIT with
+ * NFCS_ACL_NO_MATCH, and the frame is not read. Two ports may share a list. Inside a list everything is as
+ * in nfcs_acl above: the order given is the scan order, the first match decides, a REDIRECT rule without a
+ * port decides NFCS_ACL_DENY at that rule, the address masks are kept, nfcs_acl_rule's byte order holds. The
+ * reported rule index counts inside the port's list.
+ * What nfcs_aclset_commit lays out. `ports` = the highest bound port id + 1 (a binding to NFCS_ACL_LIST_NONE
+ * is no binding). Every non-empty list that is set, bound or not, lies once, in list-id order, in ONE array
+ * of compiled rules, each padded to a multiple of 4 with rules that match nothing, and each port has one
+ * 8-byte record {first rule, padded count}; a port without a list reads count 0. The padded total must be at
+ * most NFCS_ACL_MAX_RULES (the kernel stages the array in LDS), else nfcs_aclset_commit returns NFCS_EINVAL.
+ * Argument errors (NFCS_EINVAL): a list id at or above NFCS_ACLSET_MAX_LISTS; a port at or above
+ * NFCS_L2_MAX_PORTS; more than NFCS_ACL_MAX_RULES rules in one list; a rule nfcs_acl_set_rules would refuse.
+ * Setters (set_list, remove_list, bind_port, clear), commit and upload behave exactly as in nfcs_acl, nfcs_fdb
+ * and nfcs_egress: a setter invalidates an earlier commit, so the host functions return NFCS_EINVAL until the
+ * next nfcs_aclset_commit; it does NOT invalidate an earlier upload. The set is destroyed before the ctx. */
+#define NFCS_ACLSET_MAX_LISTS 128u     /* list ids 0..127 */
+#define NFCS_ACL_LIST_NONE 0xFFFFFFFFu /* nfcs_aclset_bind_port: unbind */
+#define NFCS_ACL_NO_PORT 4u /* d_action: d_port[i] was NFCS_IF_NONE; descriptor and frame not looked at */
+typedef struct nfcs_aclset nfcs_aclset;
+NFCS_API int nfcs_aclset_create(nfcs_aclset** out);
+NFCS_API int nfcs_aclset_destroy(nfcs_aclset* set); /* also frees what nfcs_aclset_upload allocated */
+/* Replaces list list_id with a copy of rules[0..n); n == 0 is an existing, empty list. */
+NFCS_API int nfcs_aclset_set_list(nfcs_aclset* set, uint32_t list_id, const nfcs_acl_rule* rules, uint32_t n);
+/* AclManager::delete_acl: the list is gone, bindings to it stay (and read "no list"). */
+NFCS_API int nfcs_aclset_remove_list(nfcs_aclset* set, uint32_t list_id);
+/* apply_acl_to_interface(port, name, EGRESS); NFCS_ACL_LIST_NONE unbinds. The list need not exist. */
+NFCS_API int nfcs_aclset_bind_port(nfcs_aclset* set, uint32_t port_id, uint32_t list_id);
+NFCS_API int nfcs_aclset_clear(nfcs_aclset* set); /* forgets every list and every binding */
+NFCS_API int nfcs_aclset_commit(nfcs_aclset* set);
+/* Copies the committed arrays to ctx's device (synchronous; replaces an earlier upload, which must no
+ * longer be in use). NFCS_EINVAL before nfcs_aclset_commit. */
+NFCS_API int nfcs_aclset_upload(nfcs_ctx* ctx, nfcs_aclset* set);
+/* The committed layout: *ports, *lists (the non-empty lists laid out) and *rules_padded (their padded
+ * total); each may be NULL. */
+NFCS_API int nfcs_aclset_info(const nfcs_aclset* set, uint32_t* ports, uint32_t* lists, uint32_t* rules_padded);
+/* The decision for one frame leaving through `port`, on the CPU, from the arrays the kernel reads; the
+ * outputs as in nfcs_acl_eval_host, *rule_index inside the port's list. frame may be NULL when len is 0. */
+NFCS_API int nfcs_aclset_eval_host(const nfcs_aclset* set, uint32_t port, const uint8_t* frame, uint32_t len,
+                                   uint32_t* action, uint32_t* rule_index, uint32_t* redirect_port);
+
+/* The egress ACL over device-resident frames: one kernel, read-only on the frames (bytes 0..95 of each at
+ * most), asynchronous on the stream. It runs after nfcs_vlan_device and before nfcs_egress_enqueue_device,
+ * on the plan's d_port and on the descriptors as the VLAN call left them (the reference evaluates the frame
+ * after the pop, with its new length); the burst may be the packets themselves or the item list of
+ * nfcs_flood_expand_device, where each flood copy then meets its own port's list (switch.hpp:188-190).
+ * Per packet, in this order:
+ *   d_port[i] == NFCS_IF_NONE      NFCS_ACL_NO_PORT; neither descriptor nor frame is looked at, d_port[i] stays
+ *   the descriptor reaches outside the arena
+ *                                  NFCS_ACL_BAD_DESC; d_port[i] = NFCS_IF_NONE; nothing is counted
+ *   the port has no list           NFCS_ACL_PERMIT, NFCS_ACL_NO_MATCH; no frame byte is loaded
+ *   otherwise the list is scanned  NFCS_ACL_DENY: d_port[i] = NFCS_IF_NONE, so the enqueue reads NFCS_EQ_SKIP
+ *                                  and the packet takes no queue depth, and with the counter arrays given
+ *                                  d_denied_pkts[port] += 1, d_denied_bytes[port] += len (the reference's
+ *                                  _increment_tx_stats(port, len, false, true), switch.hpp:126, raises
+ *                                  tx_packets, tx_bytes and tx_drops alike);
+ *                                  NFCS_ACL_REDIRECT: reported in d_action / d_redirect, d_port[i] kept (the
+ *                                  reference's egress path treats REDIRECT as PERMIT);
+ *                                  NFCS_ACL_PERMIT: d_port[i] kept.
+ *   d_port          n u32, IN/OUT: written only where stated above (stores, never a read-modify-write of
+ *                   other entries)
+ *   d_action        n bytes NFCS_ACL_*, required
+ *   d_rule          optional (NULL) n u32: the deciding rule's index inside the port's list, or NFCS_ACL_NO_MATCH
+ *   d_redirect      optional (NULL) n u32: the port for NFCS_ACL_REDIRECT, else NFCS_IF_NONE
+ *   d_denied_pkts   optional `ports` u32 (as nfcs_aclset_info reports), IN/OUT: accumulates across calls
+ *   d_denied_bytes  optional `ports` u64, IN/OUT; both counter arrays or neither, else NFCS_EINVAL. The sums
+ *                   are integers added atomically, so the result does not depend on the order.
+ * n == 0 returns NFCS_OK without a launch. set must be uploaded to ctx (else NFCS_EINVAL) and stay unchanged
+ * until the call completes. A wave whose packets all leave by one port runs nfcs_acl_eval_device's scan;
+ * a wave with several lists scans each of them once.
+ * OUT OF SCOPE: the ingress ACL's REDIRECT path; choosing the INGRESS list per packet; interface RX / TX
+ * counters other than the deny counters above. */
+NFCS_API int nfcs_egress_acl_device(nfcs_ctx* ctx, const nfcs_aclset* set, const uint8_t* d_arena,
+                                    uint64_t arena_bytes, const nfcs_desc* d_desc, uint32_t n, uint32_t* d_port,
+                                    uint8_t* d_action, uint32_t* d_rule, uint32_t* d_redirect,
+                                    uint32_t* d_denied_pkts, uint64_t* d_denied_bytes, void* stream);
+/* The same on the CPU (host arrays, same meanings; rule, redirect and the counter pair may be NULL).
+ * NFCS_EINVAL before nfcs_aclset_commit. */
+NFCS_API int nfcs_egress_acl_host(const nfcs_aclset* set, const uint8_t* arena, uint64_t arena_bytes,
+                                  const nfcs_desc* desc, uint32_t n, uint32_t* port, uint8_t* action,
+                                  uint32_t* rule, uint32_t* redirect, uint32_t* denied_pkts,
+                                  uint64_t* denied_bytes);
+
 /* ---- TX queues: persistent rings and the dequeue scheduler --------------------------------------- */
 
 /* The queues behind QosManager::enqueue_packet (qos_manager.cpp:111-153) and the scheduler of
@@ -897,7 +992,8 @@ NFCS_API int nfcs_egress_enqueue_host(const nfcs_egress* eg, const uint32_t* por
  * The object is state: calls on one nfcs_txq from two streams (or threads) at once are the caller's error.
  * OUT OF SCOPE: token buckets and rate limits; weights having any effect; interface TX counters (the
  * handle is opaque; a caller using descriptor handles can sum len from d_tx); queue contents surviving a
- * re-commit of the egress table (a re-commit wants a new nfcs_txq); per-port egress ACLs. */
+ * re-commit of the egress table (a re-commit wants a new nfcs_txq). Per-port egress ACLs run before the
+ * enqueue (nfcs_egress_acl_device): a denied packet never reaches a ring. */
 enum { NFCS_SCHED_STRICT_PRIORITY = 0, NFCS_SCHED_WRR = 1, NFCS_SCHED_DRR = 2 };
 typedef struct nfcs_txq nfcs_txq;
 

@@ -59,6 +59,10 @@ ACL_RULE_DTYPE = np.dtype([("fields", "<u4"), ("rule_id", "<u4"), ("src_mac", "u
                            ("src_ip_mask", "<u4"), ("dst_ip_mask", "<u4"), ("src_port", "<u2"), ("dst_port", "<u2"),
                            ("protocol", "u1"), ("action", "u1"), ("pad", "u1", (2,)), ("redirect_port", "<u4")])
 assert ACL_RULE_DTYPE.itemsize == 52
+# nfcs_aclset / nfcs_egress_acl_device (the egress ACLs: one list per egress port)
+ACL_NO_PORT = 4  # the packet had no egress port (IF_NONE): neither descriptor nor frame looked at
+ACL_LIST_NONE = 0xFFFFFFFF
+ACLSET_MAX_LISTS = 128
 
 # nfcs_l2_lookup_device / nfcs_fdb_lookup_host (include/nfcs.h NFCS_L2_*)
 (L2_FORWARD, L2_BAD_DESC, L2_SKIP, L2_NO_ETH, L2_FLOOD, L2_DROP_SAME_PORT, L2_DROP_LINK_DOWN, L2_DROP_STP,
@@ -226,6 +230,18 @@ def _declare(L):
         "nfcs_egress_enqueue_host": ([_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
         "nfcs_egress_plan_device": ([_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
         "nfcs_egress_enqueue_device": ([_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+        "nfcs_aclset_create": ([ctypes.POINTER(_vp)], ctypes.c_int),
+        "nfcs_aclset_destroy": ([_vp], ctypes.c_int),
+        "nfcs_aclset_set_list": ([_vp, _u32, _vp, _u32], ctypes.c_int),
+        "nfcs_aclset_remove_list": ([_vp, _u32], ctypes.c_int),
+        "nfcs_aclset_bind_port": ([_vp, _u32, _u32], ctypes.c_int),
+        "nfcs_aclset_clear": ([_vp], ctypes.c_int),
+        "nfcs_aclset_commit": ([_vp], ctypes.c_int),
+        "nfcs_aclset_upload": ([_vp, _vp], ctypes.c_int),
+        "nfcs_aclset_info": ([_vp] + [ctypes.POINTER(_u32)] * 3, ctypes.c_int),
+        "nfcs_aclset_eval_host": ([_vp, _u32, _vp, _u32] + [ctypes.POINTER(_u32)] * 3, ctypes.c_int),
+        "nfcs_egress_acl_host": ([_vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+        "nfcs_egress_acl_device": ([_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
         "nfcs_txq_create": ([_vp, _vp, ctypes.POINTER(_vp)], ctypes.c_int),
         "nfcs_txq_destroy": ([_vp], ctypes.c_int),
         "nfcs_txq_set_scheduler": ([_vp, _u32, _u32], ctypes.c_int),
@@ -416,6 +432,100 @@ class Acl:
     def close(self):
         if getattr(self, "ptr", None):
             lib().nfcs_acl_destroy(self.ptr)
+            self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AclSet:
+    """The egress ACLs behind Engine.egress_acl_device (nfcs_aclset): rule lists by id (0..ACLSET_MAX_LISTS-1,
+    ACL_RULE_DTYPE records as in Acl) and port -> list bindings. A port that is unbound, bound to a list that
+    was never set or was removed, or bound to an empty list has no list: every frame is permitted unread.
+    All non-empty lists together, each padded to ACL_GROUP, hold at most ACL_MAX_RULES rules (commit)."""
+
+    def __init__(self):
+        p = _vp()
+        _check(lib().nfcs_aclset_create(ctypes.byref(p)), "nfcs_aclset_create")
+        self.ptr = p.value
+
+    def set_list(self, list_id: int, rules):
+        """Replace list list_id; no rules is an existing, empty list."""
+        rules = np.ascontiguousarray(rules, dtype=ACL_RULE_DTYPE)
+        _check(lib().nfcs_aclset_set_list(self.ptr, int(list_id), rules.ctypes.data if len(rules) else None,
+                                          len(rules)), "nfcs_aclset_set_list")
+        return self
+
+    def remove_list(self, list_id: int):
+        """AclManager::delete_acl: bindings to the list stay and read "no list"."""
+        _check(lib().nfcs_aclset_remove_list(self.ptr, int(list_id)), "nfcs_aclset_remove_list")
+        return self
+
+    def bind_port(self, port_id: int, list_id: int):
+        """apply_acl_to_interface(port, list, EGRESS); ACL_LIST_NONE unbinds."""
+        _check(lib().nfcs_aclset_bind_port(self.ptr, int(port_id), int(list_id)), "nfcs_aclset_bind_port")
+        return self
+
+    def clear(self):
+        _check(lib().nfcs_aclset_clear(self.ptr), "nfcs_aclset_clear")
+        return self
+
+    def commit(self):
+        _check(lib().nfcs_aclset_commit(self.ptr), "nfcs_aclset_commit")
+        return self
+
+    def upload(self, engine: "Engine"):
+        """Copy the committed arrays to the engine's device; close the AclSet before the engine."""
+        _check(lib().nfcs_aclset_upload(engine.ctx, self.ptr), "nfcs_aclset_upload")
+        return self
+
+    def info(self) -> tuple[int, int, int]:
+        """(ports = highest bound port id + 1, lists laid out, their padded rule total)."""
+        a, b, c = _u32(), _u32(), _u32()
+        _check(lib().nfcs_aclset_info(self.ptr, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "nfcs_aclset_info")
+        return int(a.value), int(b.value), int(c.value)
+
+    def eval_host(self, port: int, frame: bytes) -> tuple[int, int, int]:
+        """(action, index of the deciding rule inside the port's list or ACL_NO_MATCH, redirect port or
+        IF_NONE) for one frame leaving through port, on the CPU (nfcs_aclset_eval_host)."""
+        a, r, p = _u32(), _u32(), _u32()
+        frame = bytes(frame)
+        _check(lib().nfcs_aclset_eval_host(self.ptr, int(port), frame if frame else None, len(frame), ctypes.byref(a),
+                                           ctypes.byref(r), ctypes.byref(p)), "nfcs_aclset_eval_host")
+        return int(a.value), int(r.value), int(p.value)
+
+    def egress_acl_host(self, arena, desc, port, denied_pkts=None, denied_bytes=None) -> dict:
+        """nfcs_egress_acl_host over host arrays: returns port (a copy, IF_NONE stored where the packet is
+        denied or its descriptor is bad), action (u8), rule and redirect (u32). denied_pkts (`ports` u32) and
+        denied_bytes (`ports` u64), both or neither, are updated in place."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        desc = np.ascontiguousarray(desc, dtype=DESC_DTYPE)
+        port = np.array(port, dtype=np.uint32)
+        n = len(desc)
+        assert len(port) == n
+        for a, dt in ((denied_pkts, np.uint32), (denied_bytes, np.uint64)):
+            assert a is None or (a.dtype == dt and a.flags.c_contiguous and a.flags.writeable)
+        action = np.zeros(n, np.uint8)
+        rule = np.zeros(n, np.uint32)
+        redirect = np.zeros(n, np.uint32)
+        cp = lambda a: None if a is None else a.ctypes.data
+        _check(lib().nfcs_egress_acl_host(self.ptr, arena.ctypes.data, arena.nbytes, desc.ctypes.data, n,
+                                          port.ctypes.data, action.ctypes.data, rule.ctypes.data, redirect.ctypes.data,
+                                          cp(denied_pkts), cp(denied_bytes)), "nfcs_egress_acl_host")
+        return {"port": port, "action": action, "rule": rule, "redirect": redirect}
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            lib().nfcs_aclset_destroy(self.ptr)
             self.ptr = None
 
     def __enter__(self):
@@ -981,6 +1091,18 @@ class Engine:
         _check(lib().nfcs_egress_enqueue_device(self.ctx, egress.ptr, ptr(port), ptr(queue), n, ptr(depth), ptr(result),
                                                 ptr(order), ptr(key_start), ptr(key_dropped), stream),
                "nfcs_egress_enqueue_device")
+
+    def egress_acl_device(self, aclset: "AclSet", arena, arena_bytes: int, desc, n: int, port, action, rule=None,
+                          redirect=None, denied_pkts=None, denied_bytes=None, stream=None):
+        """The egress ACL per frame on device frames, read-only, the list chosen by the packet's egress port:
+        between vlan_device and egress_enqueue_device, on the plan's port (n u32, in/out: IF_NONE stored where
+        the packet is denied or its descriptor is bad, the rest untouched). action = n bytes ACL_* (ACL_NO_PORT
+        where port was IF_NONE); rule (n u32, inside the port's list), redirect (n u32) and the deny counters
+        (denied_pkts: `ports` u32, denied_bytes: `ports` u64, both or neither, accumulating) optional."""
+        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
+        _check(lib().nfcs_egress_acl_device(self.ctx, aclset.ptr, ptr(arena), arena_bytes, ptr(desc), n, ptr(port),
+                                            ptr(action), ptr(rule), ptr(redirect), ptr(denied_pkts), ptr(denied_bytes),
+                                            stream), "nfcs_egress_acl_device")
 
     def txq_append_device(self, txq: "TxQueues", order, key_start, depth, n: int, handle=None, desc=None, stream=None):
         """enqueue_packet's emplace_back for the burst on the device copy of txq, after egress_enqueue_device

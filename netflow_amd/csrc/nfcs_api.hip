@@ -1676,6 +1676,172 @@ NFCS_API int nfcs_egress_enqueue_device(nfcs_ctx* c, const nfcs_egress* g, const
     return NFCS_OK;
 }
 
+// ---- Egress ACLs (nfcs_aclset.h: lists, bindings, compile, host decision) and their kernel ---------
+}  // extern "C"
+
+struct nfcs_aclset {
+    nfcs::AclSetInputs in;
+    nfcs::AclSetTables t;
+    bool committed = false;
+    // nfcs_aclset_upload: one device allocation holding the three arrays, on `device`
+    int device = -1;
+    uint8_t* d_blob = nullptr;
+    nfcs::AclSetDev dev;
+    bool uploaded = false;
+};
+
+namespace {
+void aclset_drop_upload(nfcs_aclset* s) {
+    if (s->d_blob) {
+        DeviceGuard dg_(s->device);
+        if (dg_.err == hipSuccess) (void)hipFree(s->d_blob);
+    }
+    s->d_blob = nullptr;
+    s->dev = nfcs::AclSetDev{};
+    s->uploaded = false;
+}
+}  // namespace
+
+extern "C" {
+
+NFCS_API int nfcs_aclset_create(nfcs_aclset** out) {
+    if (!out) return NFCS_EINVAL;
+    *out = new (std::nothrow) nfcs_aclset();
+    return *out ? NFCS_OK : NFCS_ENOMEM;
+}
+
+NFCS_API int nfcs_aclset_destroy(nfcs_aclset* s) {
+    if (!s) return NFCS_EINVAL;
+    aclset_drop_upload(s);
+    delete s;
+    return NFCS_OK;
+}
+
+// every setter: the device copy, if any, stays as it is until the next upload
+NFCS_API int nfcs_aclset_set_list(nfcs_aclset* s, uint32_t list_id, const nfcs_acl_rule* rules, uint32_t n) {
+    if (!s) return NFCS_EINVAL;
+    try {
+        const int rc = nfcs::aclset_set_list(s->in, list_id, rules, n);
+        if (rc != NFCS_OK) return rc;
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+    s->committed = false;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_aclset_remove_list(nfcs_aclset* s, uint32_t list_id) {
+    if (!s) return NFCS_EINVAL;
+    const int rc = nfcs::aclset_remove_list(s->in, list_id);
+    if (rc != NFCS_OK) return rc;
+    s->committed = false;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_aclset_bind_port(nfcs_aclset* s, uint32_t port_id, uint32_t list_id) {
+    if (!s) return NFCS_EINVAL;
+    try {
+        const int rc = nfcs::aclset_bind_port(s->in, port_id, list_id);
+        if (rc != NFCS_OK) return rc;
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+    s->committed = false;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_aclset_clear(nfcs_aclset* s) {
+    if (!s) return NFCS_EINVAL;
+    nfcs::aclset_clear(s->in);
+    s->committed = false;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_aclset_commit(nfcs_aclset* s) {
+    if (!s) return NFCS_EINVAL;
+    s->committed = false;
+    try {
+        const int rc = nfcs::aclset_compile(s->in, s->t);
+        if (rc != NFCS_OK) return rc;
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+    s->committed = true;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_aclset_upload(nfcs_ctx* c, nfcs_aclset* s) {
+    if (!c || !s || !s->committed) return NFCS_EINVAL;
+    aclset_drop_upload(s);
+    DeviceGuard dg_(c->di.device);
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    const nfcs::AclSetTables& t = s->t;
+    // one blob: the records (64 bytes each), then the actions, then the ports' bindings (8 bytes each)
+    const size_t o_act = t.rec.size() * sizeof(nfcs::AclRec), o_bind = o_act + t.act.size() * sizeof(nfcs::AclAct),
+                 total = o_bind + t.bind.size() * sizeof(nfcs::AclBind);
+    std::vector<uint8_t> blob(total + 16u, 0);
+    if (!t.rec.empty()) memcpy(blob.data(), t.rec.data(), o_act);
+    if (!t.act.empty()) memcpy(blob.data() + o_act, t.act.data(), o_bind - o_act);
+    if (!t.bind.empty()) memcpy(blob.data() + o_bind, t.bind.data(), total - o_bind);
+    NFCS_HIP(hipMalloc(&s->d_blob, blob.size()));
+    s->device = c->di.device;
+    const hipError_t e = hipMemcpy(s->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        aclset_drop_upload(s);
+        return hip_fail(e);
+    }
+    s->dev.rec = (const uint4*)s->d_blob;
+    s->dev.act = (const uint2*)(s->d_blob + o_act);
+    s->dev.bind = (const uint2*)(s->d_blob + o_bind);
+    s->dev.ports = t.ports;
+    s->dev.rules_padded = (uint32_t)t.rec.size();
+    s->uploaded = true;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_aclset_info(const nfcs_aclset* s, uint32_t* ports, uint32_t* lists, uint32_t* rules_padded) {
+    if (!s || !s->committed) return NFCS_EINVAL;
+    if (ports) *ports = s->t.ports;
+    if (lists) *lists = s->t.lists;
+    if (rules_padded) *rules_padded = (uint32_t)s->t.rec.size();
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_aclset_eval_host(const nfcs_aclset* s, uint32_t port, const uint8_t* frame, uint32_t len,
+                                   uint32_t* action, uint32_t* rule_index, uint32_t* redirect_port) {
+    if (!s || !s->committed || (len > 0 && !frame)) return NFCS_EINVAL;
+    nfcs::aclset_decide(s->t, port, frame, len, action, rule_index, redirect_port);
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_egress_acl_host(const nfcs_aclset* s, const uint8_t* arena, uint64_t arena_bytes,
+                                  const nfcs_desc* desc, uint32_t n, uint32_t* port, uint8_t* action, uint32_t* rule,
+                                  uint32_t* redirect, uint32_t* denied_pkts, uint64_t* denied_bytes) {
+    if (!s || !s->committed || (!denied_pkts != !denied_bytes)) return NFCS_EINVAL;
+    if (n == 0) return NFCS_OK;
+    if (!arena || !desc || !port || !action) return NFCS_EINVAL;
+    nfcs::aclset_egress(s->t, arena, arena_bytes, desc, n, port, action, rule, redirect, denied_pkts, denied_bytes);
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_egress_acl_device(nfcs_ctx* c, const nfcs_aclset* s, const uint8_t* d_arena, uint64_t arena_bytes,
+                                    const nfcs_desc* d_desc, uint32_t n, uint32_t* d_port, uint8_t* d_action,
+                                    uint32_t* d_rule, uint32_t* d_redirect, uint32_t* d_denied_pkts,
+                                    uint64_t* d_denied_bytes, void* stream) {
+    if (!c || !s || !s->uploaded || s->device != c->di.device) return NFCS_EINVAL;
+    if (!d_denied_pkts != !d_denied_bytes) return NFCS_EINVAL;
+    DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    if (n == 0) return NFCS_OK;
+    if (!d_arena || !d_desc || !d_port || !d_action || ((uintptr_t)d_arena & 15u)) return NFCS_EINVAL;
+    if (((uintptr_t)d_port & 3u) || ((uintptr_t)d_rule & 3u) || ((uintptr_t)d_redirect & 3u) ||
+        ((uintptr_t)d_denied_pkts & 3u) || ((uintptr_t)d_denied_bytes & 7u))
+        return NFCS_EINVAL;
+    NFCS_HIP(nfcs::launch_egress_acl(c->di, s->dev, d_arena, arena_bytes, d_desc, n, d_port, d_action, d_rule, d_redirect,
+                                     d_denied_pkts, d_denied_bytes, pick(c, stream)));
+    return NFCS_OK;
+}
+
 // ---- TX queues (nfcs_txq.h: tables, host state, the walks and the closed form) and their kernels ------
 }  // extern "C"
 

@@ -7,6 +7,7 @@
 
 #include "nfcs.h"
 #include "nfcs_acl.h"
+#include "nfcs_aclset.h"
 #include "nfcs_egress.h"
 #include "nfcs_fdb.h"
 #include "nfcs_fib.h"
@@ -214,6 +215,18 @@ struct AclDev {
 hipError_t launch_acl_eval(const DevInfo& di, const AclDev& acl, const uint8_t* arena, uint64_t arena_bytes,
                            const nfcs_desc* desc, uint32_t n, uint8_t* action, uint32_t* rule, uint32_t* redirect,
                            uint32_t* nh, hipStream_t stream);
+
+// The committed ACL set in device memory (nfcs_aclset_upload; the arrays of AclSetTables, nfcs_aclset.h).
+struct AclSetDev {
+    const uint4* rec = nullptr;   // rules_padded 64-byte records, every list one behind the other
+    const uint2* act = nullptr;   // rules_padded {action, redirect port}, indexed like rec
+    const uint2* bind = nullptr;  // ports {first rule, padded count}; count 0 = no list
+    uint32_t ports = 0, rules_padded = 0;
+};
+
+hipError_t launch_egress_acl(const DevInfo& di, const AclSetDev& set, const uint8_t* arena, uint64_t arena_bytes,
+                             const nfcs_desc* desc, uint32_t n, uint32_t* port, uint8_t* action, uint32_t* rule,
+                             uint32_t* redirect, uint32_t* denied_pkts, uint64_t* denied_bytes, hipStream_t stream);
 
 // The committed L2 tables in device memory (nfcs_fdb_upload; the arrays of FdbTables, nfcs_fdb.h).
 struct FdbDev {

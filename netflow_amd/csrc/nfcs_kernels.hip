@@ -2423,6 +2423,232 @@ hipError_t launch_acl_eval(const DevInfo& di, const AclDev& acl, const uint8_t* 
     return hipGetLastError();
 }
 
+// ---- Egress ACLs: the list chosen per packet by its egress port -----------------
+// acl_eval_kernel's shape (64 packets per wave, one lane each; header chunks 0..2 in 8-lane rows; the late
+// chunks; every rule staged once per workgroup behind the header rows), with the rule list taken from the
+// packet's egress port: lane l gathers its port's binding {first rule, padded count} (the binding array is
+// small and reused: default cache policy). A lane whose packet needs no scan — no port, a descriptor
+// outside the arena, a port without a list — requests no frame bytes (its row loads read the zero line), and
+// a wave without any scan skips rows, keys and scan. The scan is a waterfall over the lists present in the
+// wave: take the binding of the first pending lane (readfirstlane), run acl_eval_kernel's wave-uniform scan
+// over that list's range for the lanes bound to it, retire them, repeat. Every list is scanned at most once
+// per wave, and a wave whose packets all leave by one port runs exactly the single-list loop.
+// Deny counters: the denied lanes of a wave are grouped by port (the same waterfall), each group's lengths
+// are summed in a 64-bit LDS slot of its first lane, and that lane adds the group's count and sum to the
+// port's counters: one pair of global atomics per distinct denied port per wave.
+constexpr uint32_t kEaSlotsBytes = kWavesPerBlock * 64u * 8u;  // one u64 per lane
+static_assert(kAclRowsBytes + kEaSlotsBytes + NFCS_ACL_MAX_RULES * sizeof(AclRec) < 64u * 1024u,
+              "header rows + sum slots + rules stay under 64 KiB of dynamic LDS (no opt-in needed)");
+
+__global__ __launch_bounds__(kBlock) void egress_acl_kernel(const nfcs_desc* __restrict__ desc, uint32_t n,
+                                                            uint32_t nblocks, const uint8_t* __restrict__ arena,
+                                                            uint64_t arena_bytes, uint32_t* __restrict__ port_io,
+                                                            const AclSetDev set, uint8_t* __restrict__ action_out,
+                                                            uint32_t* __restrict__ rule_out,
+                                                            uint32_t* __restrict__ redirect_out,
+                                                            uint32_t* __restrict__ denied_pkts,
+                                                            unsigned long long* __restrict__ denied_bytes) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t ea_lds[];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t p0 = ((uint64_t)xcd_block_n(nblocks) * kWavesPerBlock + rfl(wave)) * 64u;
+    uint8_t* rows = ea_lds + wave * 64u * kFkRow;
+    // lane l: port and descriptor of packet p0 + l (coalesced loads), then its port's binding
+    const uint64_t p = p0 + lane;
+    uint2 dl = make_uint2(0u, 0u);
+    uint32_t port = NFCS_IF_NONE;
+    if (p < n) {
+        dl = ((const uint2*)desc)[p];
+        port = port_io[p];
+    }
+    const bool has_port = port != NFCS_IF_NONE;  // false past n; without a port the descriptor means nothing
+    const uint64_t off = (uint64_t)dl.x * 16u;
+    const bool live = has_port && off + (((uint64_t)dl.y + 15u) & ~15ull) <= arena_bytes;
+    uint2 bind = make_uint2(0u, 0u);
+    if (live && port < set.ports) bind = set.bind[port];
+    const bool scan = bind.y != 0u;  // the frame is read only for these
+    const uint32_t len = scan ? dl.y : 0u;
+    const bool any = __builtin_amdgcn_ballot_w64(scan) != 0;  // wave-uniform
+    // header chunks 0..2 in 8-lane rows (instruction k, row r -> packet 8k + r, lane rl -> chunk rl),
+    // non-temporal: the frames are read once
+    const uint32_t rl = lane & 7u, r = lane >> 3;
+    const uint4* zl = g_zero_line;
+    uint4 c[8];
+    if (any) {
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) {
+            const uint32_t q = 8u * k + r;
+            const uint32_t qo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)dl.x);
+            const uint32_t ql = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)len);
+            const uint4* src = (const uint4*)(arena + (uint64_t)qo * 16u);
+            c[k] = ld16<1>((rl < 3u && rl * 16u < ql) ? src + rl : zl);
+        }
+    }
+    // every list's compiled rules, four 16-byte pieces each, once per workgroup (every wave of the
+    // workgroup takes part, also one past n or without a scan: it reaches the barrier)
+    uint4* rec4 = (uint4*)(ea_lds + kAclRowsBytes + kEaSlotsBytes);
+    const uint32_t n4 = set.rules_padded * 4u;
+    for (uint32_t i0 = 0; i0 < n4; i0 += 4u * kBlock) {  // 4 loads in flight per lane (index clamped, not branched)
+        uint4 t[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t i = i0 + j * kBlock + threadIdx.x;
+            t[j] = set.rec[i < n4 ? i : n4 - 1u];
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t i = i0 + j * kBlock + threadIdx.x;
+            if (i < n4) rec4[i] = t[j];
+        }
+    }
+    __syncthreads();
+    if (p0 >= n) return;
+    uint32_t match = NFCS_ACL_NO_MATCH;  // an index into the one array
+    if (any) {
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k)
+            if (rl < 3u) *(uint4*)(rows + (8u * k + r) * kFkRow + 16u * rl) = c[k];
+        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes are done
+        __builtin_amdgcn_wave_barrier();
+        // lane l builds the key of packet l (nfcs_acl.h acl_key, the same bounds); len is 0 without a scan
+        uint8_t* b = rows + lane * kFkRow;
+        const uint32_t e12 = lds_be16(b, 12);
+        const bool eth = len >= 14, tagged = e12 == 0x8100u;
+        const uint32_t sh = tagged ? 4u : 0u;  // l2 = 18 behind a tag
+        const bool known = eth && (!tagged || len >= 18);
+        const uint32_t et = !known ? 0u : tagged ? lds_be16(b, 16) : e12;
+        const bool v4 = known && et == 0x0800u && 34u + sh <= len;  // ipv4() present
+        const uint32_t l4 = 14u + sh + (lds_u8(b, 14u + sh) & 15u) * 4u;
+        {  // the ports end at l4 + 4: past byte 47 only with IPv4 options (IHL >= 8; 7 behind a tag)
+            const bool more = v4 && l4 + 4u > 48u && len > 48u;
+            if (__builtin_amdgcn_ballot_w64(more) != 0) {
+                if (more) {
+                    const uint4* src = (const uint4*)(arena + off);
+#pragma unroll
+                    for (uint32_t j = 3; j < 6; ++j) *(uint4*)(b + 16u * j) = ld16<0>(16u * j < len ? src + j : zl);
+                }
+                __builtin_amdgcn_s_waitcnt(0xc07f);
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+        uint32_t key[8];
+        key[kAkMac0] = eth ? *(const uint32_t*)b : 0u;
+        key[kAkMac1] = eth ? *(const uint32_t*)(b + 4) : 0u;
+        key[kAkMac2] = eth ? *(const uint32_t*)(b + 8) : 0u;
+        const bool has_vid = eth && tagged && len >= 18;
+        key[kAkL2] = (has_vid ? lds_be16(b, 14) & 0x0FFFu : 0u) | (et << 16);
+        uint32_t meta = (eth ? kApEth : 0u) | (has_vid ? kApVlan : 0u) | (known ? kApEtype : 0u);
+        uint32_t sip = 0, dip = 0, ports = 0;
+        if (v4) {
+            sip = __builtin_bswap32(lds_le32(b, 26u + sh));  // ntohl: AclRule holds host order
+            dip = __builtin_bswap32(lds_le32(b, 30u + sh));
+            const uint32_t proto = lds_u8(b, 23u + sh);
+            meta |= kApIpv4 | proto;
+            // tcp() needs l4 + 19 <= len (19-byte TcpHeader), udp() l4 + 8 (packet.hpp:473-541)
+            if ((proto == 6 && l4 + 19u <= len) || (proto == 17 && l4 + 8u <= len)) {
+                meta |= kApPorts;
+                ports = lds_be16(b, l4) | (lds_be16(b, l4 + 2u) << 16);
+            }
+        }
+        key[kAkSrcIp] = sip;
+        key[kAkDstIp] = dip;
+        key[kAkPorts] = ports;
+        key[kAkMeta] = meta;
+        // the waterfall: one wave-uniform scan per list present in the wave
+        const uint4* rec = (const uint4*)(ea_lds + kAclRowsBytes + kEaSlotsBytes);
+        bool pending = scan;
+        while (__builtin_amdgcn_ballot_w64(pending) != 0) {
+            if (pending) {  // among the pending lanes, the first one's list (lists are disjoint, non-empty ranges)
+                const uint32_t first = rfl(bind.x), end = first + rfl(bind.y);
+                const bool mine = bind.x == first;
+                for (uint32_t i = first; i < end; i += kAclGroup) {
+                    if (__builtin_amdgcn_ballot_w64(mine && match == NFCS_ACL_NO_MATCH) == 0) break;
+                    // as in acl_eval_kernel: dwords 4..7 first, dwords 0..3 only when a rule of the trip tests them
+                    uint32_t d[kAclGroup], l2 = 0;
+#pragma unroll
+                    for (uint32_t j = 0; j < kAclGroup; ++j) {
+                        const uint4* e = rec + (i + j) * 4u;
+                        const uint4 v1 = e[1], m1 = e[3];
+                        d[j] = (key[4] ^ v1.x) & m1.x;
+                        d[j] |= (key[5] ^ v1.y) & m1.y;
+                        d[j] |= (key[6] ^ v1.z) & m1.z;
+                        d[j] |= (key[7] ^ v1.w) & m1.w;
+                        l2 |= m1.w;
+                    }
+                    if (rfl(l2) & kApNeedL2) {
+#pragma unroll
+                        for (uint32_t j = 0; j < kAclGroup; ++j) {
+                            const uint4* e = rec + (i + j) * 4u;
+                            const uint4 v0 = e[0], m0 = e[2];
+                            d[j] |= (key[0] ^ v0.x) & m0.x;
+                            d[j] |= (key[1] ^ v0.y) & m0.y;
+                            d[j] |= (key[2] ^ v0.z) & m0.z;
+                            d[j] |= (key[3] ^ v0.w) & m0.w;
+                        }
+                    }
+                    uint32_t m = NFCS_ACL_NO_MATCH;
+#pragma unroll
+                    for (uint32_t j = kAclGroup; j-- > 0;) m = d[j] == 0 ? i + j : m;  // descending: the first rule wins
+                    match = (mine && match == NFCS_ACL_NO_MATCH) ? m : match;
+                }
+                if (mine) pending = false;
+            }
+        }
+    }
+    uint32_t action = !has_port ? NFCS_ACL_NO_PORT : live ? NFCS_ACL_PERMIT : NFCS_ACL_BAD_DESC;
+    uint32_t redirect = NFCS_IF_NONE, rule = NFCS_ACL_NO_MATCH;
+    if (match != NFCS_ACL_NO_MATCH) {  // a scanned lane; match < set.rules_padded and no padding rule matches
+        const uint2 a = set.act[match];
+        action = a.x;
+        redirect = a.y;
+        rule = match - bind.x;
+    }
+    const bool denied = action == NFCS_ACL_DENY;
+    if (p < n) {  // one packet per lane: each store instruction writes consecutive elements
+        action_out[p] = (uint8_t)action;
+        if (rule_out) rule_out[p] = rule;
+        if (redirect_out) redirect_out[p] = redirect;
+        if (denied || action == NFCS_ACL_BAD_DESC) port_io[p] = NFCS_IF_NONE;  // a predicated store
+    }
+    if (denied_pkts && __builtin_amdgcn_ballot_w64(denied) != 0) {  // denied lanes had a list: port < set.ports
+        unsigned long long* slot = (unsigned long long*)(ea_lds + kAclRowsBytes) + wave * 64u;
+        uint32_t lead = lane, cnt = 0;
+        bool dp = denied;
+        while (__builtin_amdgcn_ballot_w64(dp) != 0) {
+            if (dp) {
+                const uint32_t lp = rfl(port);  // the first pending lane's port
+                if (port == lp) {               // its group
+                    const uint64_t grp = __builtin_amdgcn_ballot_w64(true);
+                    lead = (uint32_t)__builtin_ctzll(grp);
+                    cnt = (uint32_t)__builtin_popcountll(grp);
+                    dp = false;
+                }
+            }
+        }
+        const bool leader = denied && lead == lane;
+        if (leader) slot[lane] = 0ull;
+        __builtin_amdgcn_wave_barrier();  // one wave's LDS operations execute in order
+        if (denied) atomicAdd(&slot[lead], (unsigned long long)dl.y);
+        __builtin_amdgcn_wave_barrier();
+        if (leader) {
+            atomicAdd(&denied_pkts[port], cnt);
+            atomicAdd(&denied_bytes[port], slot[lane]);
+        }
+    }
+}
+
+hipError_t launch_egress_acl(const DevInfo& di, const AclSetDev& set, const uint8_t* arena, uint64_t arena_bytes,
+                             const nfcs_desc* desc, uint32_t n, uint32_t* port, uint8_t* action, uint32_t* rule,
+                             uint32_t* redirect, uint32_t* denied_pkts, uint64_t* denied_bytes, hipStream_t stream) {
+    (void)di;
+    if (n == 0) return hipSuccess;
+    // 64 packets per wave, one lane each, XCD-aware order; LDS: the header rows, the sum slots, then the rules
+    const uint32_t g = (n + 255u) / 256u;
+    const unsigned lds = kAclRowsBytes + kEaSlotsBytes + set.rules_padded * (unsigned)sizeof(AclRec);
+    hipLaunchKernelGGL(egress_acl_kernel, dim3(g), dim3(kBlock), lds, stream, desc, n, g, arena, arena_bytes, port, set,
+                       action, rule, redirect, denied_pkts, (unsigned long long*)denied_bytes);
+    return hipGetLastError();
+}
+
 // ---- L2 forwarding: FDB lookup, port / VLAN checks, learning -------------------
 // The L2 block of the switch (switch.hpp:305-326) per packet: a wave takes 64 packets, one lane each,
 // with route_lookup_kernel's descriptor load, liveness test and XCD-aware block order. Everything the
