@@ -68,6 +68,55 @@ def decide_host(fib: nf.Fib, frames):
     return v, nh, eif
 
 
+def model_lookup(routes, arp, if_macs, local_ips, dst: int, ttl: int):
+    """(verdict, egress interface, the 12 bytes dst MAC + src MAC the forward would write, or None) for one
+    destination and TTL: a plain restatement of switch.hpp:270-294 over the inputs as they were given, sharing
+    no code with the library. routes: rows {network, mask, next hop (0 = connected), interface, ...} in lookup
+    order (RoutingManager::lookup_route returns the first that matches); arp: [(ip, mac bytes)], of two
+    entries for one address the later one counts; if_macs: [(interface, mac bytes)]; addresses are the
+    tables' u32 (nf.ip4)."""
+    arp_of = {int(a): bytes(m) for a, m in arp}
+    mac_of = {int(i): bytes(m) for i, m in if_macs}
+    dst = int(dst)
+    if dst in {int(a) for a in local_ips}:                     # is_my_ip (270)
+        return nf.RT_LOCAL, nf.IF_NONE, None
+    if ttl <= 1:                                               # 279
+        return nf.RT_TTL_EXPIRED, nf.IF_NONE, None
+    for row in routes:                                         # lookup_route (282)
+        network, mask, gateway, ifid = (int(x) for x in row[:4])
+        if dst & mask != network:
+            continue
+        target = gateway if gateway != 0 else dst             # 285-286: ARP for the gateway, or the destination
+        if target not in arp_of:
+            return nf.RT_ARP_MISS, nf.IF_NONE, None
+        if ifid not in mac_of:                                 # 291-292
+            return nf.RT_NO_IF_MAC, nf.IF_NONE, None
+        return nf.RT_FORWARD, ifid, arp_of[target] + mac_of[ifid]
+    return nf.RT_NO_ROUTE, nf.IF_NONE, None
+
+
+def model_decide(routes, arp, if_macs, local_ips, frames):
+    """model_lookup behind the IPv4 predicate, per frame: verdict (u8), egress interface (u32), MAC pairs
+    ((n, 12) u8, zero unless the verdict is RT_FORWARD)."""
+    n = len(frames)
+    v, eif, macs = np.zeros(n, np.uint8), np.full(n, nf.IF_NONE, np.uint32), np.zeros((n, 12), np.uint8)
+    for i, f in enumerate(frames):
+        h = ipv4_dst_ttl(f)
+        if h is None:
+            v[i] = nf.RT_NOT_IPV4
+            continue
+        v[i], eif[i], m = model_lookup(routes, arp, if_macs, local_ips, *h)
+        if m is not None:
+            macs[i] = np.frombuffer(m, np.uint8)
+    return v, eif, macs
+
+
+def fixture_model_inputs(z, table: str):
+    """(routes, arp, if_macs, local_ips) of the fixture in the form model_lookup takes."""
+    return (z["routes_" + table], [(int(a), bytes(m)) for a, m in zip(z["arp_ip"], z["arp_mac"])],
+            [(int(i), bytes(m)) for i, m in zip(z["if_id"], z["if_mac"])], [int(a) for a in z["local_ip"]])
+
+
 def rewrite_dsts(frames, pool, rng, share=0.5):
     """Frames with the destination of `share` of ALL of them replaced by a draw from pool (u32s). Only
     frames that pass the IPv4 predicate have a destination to replace (a little over half of the
