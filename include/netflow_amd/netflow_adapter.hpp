@@ -209,6 +209,27 @@ inline int flood_expand_batch(const std::vector<netflow::Packet*>& pkts, const n
     return flood_expand_batch(pkts.data(), pkts.size(), fdb, ingress_port, num_ports, egress_port, l2_verdict, l2_vlan, out);
 }
 
+// The switch's ICMP answers for the burst route_lookup_batch just decided (ChecksumEngine::icmp_respond_batch,
+// packet.hpp): echo replies for NFCS_RT_LOCAL echo requests, ICMP 11/0 for NFCS_RT_TTL_EXPIRED and 3/0 for
+// NFCS_RT_NO_ROUTE, built and checksummed on the device, with the messages' bytes for the caller to wrap in
+// PacketBuffers of its own and hand to send_control_plane_packet(pkt, out->port[k]) — the call sites the
+// reference leaves as comments at switch.hpp:271 / 279 / 301. This overload over netflow::Packet* has not been
+// run against the reference's real types; the tested path is the same template over netflow_amd::Packet
+// (tests/cpp/icmp_respond_test.cpp).
+inline int icmp_respond_batch(netflow::Packet* const* pkts, size_t n, const nfcs_icmp* icmp, const nfcs_fib* fib,
+                              uint32_t ingress_port, const uint8_t* rt_verdict, const uint16_t* ip_id,
+                              ChecksumEngine::IcmpMessages* out) {
+    return detail::on_default_engine([&](ChecksumEngine& e) {
+        return e.icmp_respond_batch(pkts, n, icmp, fib, ingress_port, rt_verdict, ip_id, out);
+    });
+}
+// A committed nfcs_icmp from the switch's InterfaceManager (make_icmp_from, packet.hpp). A template, so that
+// <netflow++/interface_manager.hpp> is needed only where make_icmp is used.
+template <class InterfaceManagerT>
+inline int make_icmp(const InterfaceManagerT& ifm, uint32_t num_ports, nfcs_icmp** out) {
+    return make_icmp_from(ifm, num_ports, out);
+}
+
 inline int egress_plan_batch(netflow::Packet* const* pkts, size_t n, const nfcs_egress* eg, const uint32_t* egress_port,
                              uint32_t* ops, uint8_t* queue) {
     return detail::on_default_engine(

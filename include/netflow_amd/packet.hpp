@@ -298,6 +298,32 @@ public:
                            const uint32_t* egress_port, const uint8_t* l2_verdict, const uint16_t* l2_vlan,
                            FloodItems* out);
 
+    // The switch's ICMP answers (switch.hpp:271 / 279 / 301 with IcmpProcessor, icmp_processor.cpp; nfcs_icmp_respond_device)
+    // for the batch route_lookup_batch just decided, received on ingress_port: rt_verdict is that call's verdict
+    // array, ip_id (optional) the IPv4 identification per error message (the reference draws rand()). The burst is
+    // staged with tail room for the messages (bounded from the lengths, so nothing is cut). out gets the messages
+    // in the reference's order: per message the source packet's index, the port send_control_plane_packet is called
+    // with, the length and the offset of its bytes in `bytes`, checksums included, for the caller to wrap in
+    // buffers of its own; status (optional in the C ABI, always filled here) says per packet what became of it
+    // (NFCS_ICMP_ST_*). The packets are not changed. icmp and fib must be committed and uploaded (upload_icmp,
+    // upload_fib).
+    struct IcmpMessages {
+        std::vector<uint32_t> src, port, len;  // per message
+        std::vector<uint64_t> off;             // per message: offset into bytes
+        std::vector<uint8_t> bytes;            // the message region, slots of round_up(len, 16) bytes
+        std::vector<uint8_t> status;           // per packet
+        nfcs_icmp_totals totals{};
+    };
+    template <class Pkt>
+    int icmp_respond_batch(Pkt* const* pkts, size_t n, const nfcs_icmp* icmp, const nfcs_fib* fib, uint32_t ingress_port,
+                           const uint8_t* rt_verdict, const uint16_t* ip_id, IcmpMessages* out);
+    // nfcs_icmp_upload to this engine's device, serialised with its other calls. The icmp must be destroyed
+    // before the engine.
+    int upload_icmp(nfcs_icmp* icmp) {
+        std::lock_guard<std::mutex> lock(mu_);
+        return nfcs_icmp_upload(ctx_, icmp);
+    }
+
     // The egress decision (VlanManager::process_egress + QosManager::classify_packet_to_queue) for a batch
     // whose packet i leaves through egress_port[i] (NFCS_IF_NONE: none), from committed egress ports
     // (nfcs_egress_*; upload_egress first): ops[i] = NFCS_VLAN_POP or NFCS_VLAN_NOP (what process_egress
@@ -829,6 +855,73 @@ int ChecksumEngine::flood_expand_batch(Pkt* const* pkts, size_t n, const nfcs_fd
         out->len[k] = idesc[k].len;
         out->copy_off[k] = o >= copy_base && out->src[k] < n && o != (uint64_t)lay[out->src[k]].off16 * 16
                                ? o - copy_base : FloodItems::kOriginal;
+    }
+    return NFCS_OK;
+}
+
+template <class Pkt>
+int ChecksumEngine::icmp_respond_batch(Pkt* const* pkts, size_t n, const nfcs_icmp* icmp, const nfcs_fib* fib,
+                                       uint32_t ingress_port, const uint8_t* rt_verdict, const uint16_t* ip_id,
+                                       IcmpMessages* out) {
+    if (!out) return NFCS_EINVAL;
+    *out = IcmpMessages{};
+    if (n == 0) return NFCS_OK;
+    if (!pkts || !icmp || !fib || !rt_verdict || n > 0xFFFFFFFFu) return NFCS_EINVAL;
+    std::lock_guard<std::mutex> lock(mu_);
+    const uint32_t m = static_cast<uint32_t>(n);
+    // the region's bound from the lengths alone: a reply is shorter than its request, an error at most 110 bytes
+    size_t frames = 0, bound = 0;
+    for (size_t i = 0; i < n; ++i) {
+        auto* b = pkts[i] ? pkts[i]->get_buffer() : nullptr;
+        const size_t len = b ? b->get_data_length() : 0;
+        frames += (len + 15) & ~size_t(15);
+        bound += ((len + 15) & ~size_t(15)) + 112;
+    }
+    const uint64_t msg_base = (frames + 127) & ~uint64_t(127), arena_bytes = msg_base + bound;
+    if (arena_bytes / 16 > 0xFFFFFFFFu) return NFCS_EINVAL;
+    int rc = reserve(arena_bytes + 16, n);
+    if (rc) return rc;
+    gather(pkts, n, 0);
+    DevTmp dv(ctx_, n, rc);
+    DevTmp did(ctx_, n * sizeof(uint16_t), rc);
+    DevTmp dmdesc(ctx_, n * sizeof(nfcs_desc), rc);
+    DevTmp dmport(ctx_, n * sizeof(uint32_t), rc);
+    DevTmp dmsrc(ctx_, n * sizeof(uint32_t), rc);
+    DevTmp dtot(ctx_, sizeof(nfcs_icmp_totals), rc);
+    if (rc) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, d_arena_, h_arena_, frames ? frames : 16))) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, d_desc_, h_desc_, n * sizeof(nfcs_desc)))) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, dv.p, rt_verdict, n))) return rc;
+    if (ip_id && (rc = nfcs_memcpy_h2d(ctx_, did.p, ip_id, n * sizeof(uint16_t)))) return rc;
+    if ((rc = nfcs_icmp_respond_device(ctx_, icmp, fib, ingress_port, static_cast<uint8_t*>(d_arena_), arena_bytes, msg_base,
+                                       16, static_cast<nfcs_desc*>(d_desc_), m, static_cast<uint8_t*>(dv.p),
+                                       ip_id ? static_cast<uint16_t*>(did.p) : nullptr, m,
+                                       static_cast<nfcs_desc*>(dmdesc.p), static_cast<uint32_t*>(dmport.p),
+                                       static_cast<uint32_t*>(dmsrc.p), static_cast<uint8_t*>(d_status_),
+                                       static_cast<nfcs_icmp_totals*>(dtot.p), nullptr)))
+        return rc;
+    if ((rc = nfcs_memcpy_d2h(ctx_, &out->totals, dtot.p, sizeof(nfcs_icmp_totals)))) return rc;
+    const uint32_t msgs = out->totals.messages;
+    if (msgs > m || msgs != out->totals.messages_needed || out->totals.msg_bytes > bound) return NFCS_EHIP;
+    std::vector<nfcs_desc> mdesc(msgs);
+    out->src.resize(msgs);
+    out->port.resize(msgs);
+    out->len.resize(msgs);
+    out->off.resize(msgs);
+    out->status.resize(n);
+    out->bytes.resize(out->totals.msg_bytes);
+    if ((rc = nfcs_memcpy_d2h(ctx_, out->status.data(), d_status_, n))) return rc;
+    if (msgs) {
+        if ((rc = nfcs_memcpy_d2h(ctx_, mdesc.data(), dmdesc.p, msgs * sizeof(nfcs_desc)))) return rc;
+        if ((rc = nfcs_memcpy_d2h(ctx_, out->port.data(), dmport.p, msgs * sizeof(uint32_t)))) return rc;
+        if ((rc = nfcs_memcpy_d2h(ctx_, out->src.data(), dmsrc.p, msgs * sizeof(uint32_t)))) return rc;
+        if ((rc = nfcs_memcpy_d2h(ctx_, out->bytes.data(), static_cast<uint8_t*>(d_arena_) + msg_base, out->bytes.size())))
+            return rc;
+    }
+    for (uint32_t k = 0; k < msgs; ++k) {
+        out->len[k] = mdesc[k].len;
+        out->off[k] = (uint64_t)mdesc[k].off16 * 16 - msg_base;
+        if (out->off[k] + ((mdesc[k].len + 15u) & ~15u) > out->bytes.size()) return NFCS_EHIP;
     }
     return NFCS_OK;
 }
@@ -1426,6 +1519,49 @@ inline int flood_expand_batch(Packet* const* pkts, size_t n, const nfcs_fdb* fdb
     return detail::on_default_engine([&](ChecksumEngine& e) {
         return e.flood_expand_batch(pkts, n, fdb, ingress_port, num_ports, egress_port, l2_verdict, l2_vlan, out);
     });
+}
+inline int icmp_respond_batch(Packet* const* pkts, size_t n, const nfcs_icmp* icmp, const nfcs_fib* fib, uint32_t ingress_port,
+                              const uint8_t* rt_verdict, const uint16_t* ip_id, ChecksumEngine::IcmpMessages* out) {
+    return detail::on_default_engine([&](ChecksumEngine& e) {
+        return e.icmp_respond_batch(pkts, n, icmp, fib, ingress_port, rt_verdict, ip_id, out);
+    });
+}
+
+// A committed ICMP table set (nfcs_icmp) from an interface manager: per configured interface, ascending as
+// InterfaceManager scans them, every address with the interface's MAC (get_mac_for_ip), the first address
+// (get_interface_ip), and the ports below num_ports whose link is up (send_control_plane_packet's test). `ifm`
+// needs get_all_port_configs() (a map from id to a config with mac_address.bytes and ip_configurations[].address)
+// and is_port_link_up(id): netflow::InterfaceManager's names. Returns NFCS_OK and the tables in *out
+// (nfcs_icmp_destroy them; upload them with ChecksumEngine::upload_icmp), or a negative NFCS_E* code.
+template <class InterfaceManagerT>
+inline int make_icmp_from(const InterfaceManagerT& ifm, uint32_t num_ports, nfcs_icmp** out) {
+    if (!out) return NFCS_EINVAL;
+    *out = nullptr;
+    std::vector<nfcs_icmp_local> local;
+    std::vector<nfcs_icmp_if_ip> if_ips;
+    std::vector<uint32_t> up;
+    for (const auto& kv : ifm.get_all_port_configs()) {
+        const uint32_t id = static_cast<uint32_t>(kv.first);
+        for (const auto& c : kv.second.ip_configurations) {
+            nfcs_icmp_local l{};
+            l.ip = c.address;
+            std::memcpy(l.mac, kv.second.mac_address.bytes, 6);
+            local.push_back(l);
+            if_ips.push_back(nfcs_icmp_if_ip{id, c.address});
+        }
+        if (id < num_ports && ifm.is_port_link_up(id)) up.push_back(id);
+    }
+    nfcs_icmp* t = nullptr;
+    int rc = nfcs_icmp_create(&t);
+    if (rc) return rc;
+    if ((rc = nfcs_icmp_set_local(t, local.data(), static_cast<uint32_t>(local.size()))) ||
+        (rc = nfcs_icmp_set_if_ips(t, if_ips.data(), static_cast<uint32_t>(if_ips.size()))) ||
+        (rc = nfcs_icmp_set_ports_up(t, up.data(), static_cast<uint32_t>(up.size()), num_ports)) || (rc = nfcs_icmp_commit(t))) {
+        nfcs_icmp_destroy(t);
+        return rc;
+    }
+    *out = t;
+    return NFCS_OK;
 }
 inline int flow_keys_batch(Packet* const* pkts, size_t n, nfcs_flow_key* keys,
                            uint32_t* hashes = nullptr) {

@@ -713,6 +713,170 @@ NFCS_API int nfcs_flood_expand_host(const nfcs_fdb* fdb, uint32_t ingress_port, 
                                     const uint16_t* l2_vlan, uint32_t cap, nfcs_desc* item_desc, uint32_t* item_port,
                                     uint32_t* item_src, nfcs_flood_totals* totals);
 
+/* ---- ICMP: echo replies and TTL / unreachable errors built on the device --------------------- */
+
+/* The three verdicts of nfcs_route_lookup_device that the switch answers instead of dropping:
+ *   NFCS_RT_LOCAL, protocol ICMP  switch.hpp:271, IcmpProcessor::process_icmp_packet (icmp_processor.cpp:33-81)
+ *                                 -> echo reply (send_icmp_echo_reply, 83-188)
+ *   NFCS_RT_TTL_EXPIRED           switch.hpp:279, send_time_exceeded (344-348) -> ICMP 11/0
+ *   NFCS_RT_NO_ROUTE              switch.hpp:301, send_destination_unreachable(.., 0) (350-353) -> ICMP 3/0
+ *                                 (both through send_icmp_error_packet_base, 193-342)
+ * ONE call builds every message of a burst, checksums included, into a message region [msg_base, arena_bytes)
+ * at the tail of the same arena, with a compacted message list (descriptor, port, source packet) in the form
+ * of nfcs_flood_expand_device's item list. The symbols of this section were added without changing
+ * NFCS_ABI_VERSION (it stays 2): detect them by symbol lookup (dlsym "nfcs_icmp_create").
+ * OUT OF SCOPE: the ARP request the reference sends on an ARP miss (NFCS_ICMP_ST_SRC_ARP_MISS names the
+ * packet), packet_handler_ for other local traffic (NFCS_ICMP_ST_TO_CPU), ICMPv6, interface counters.
+ *
+ * Tables (nfcs_icmp). IPv4 addresses are u32 in NETWORK byte order, as in nfcs_fib.
+ *   local    InterfaceManager::get_mac_for_ip(ip) for the switch's own addresses. Of two entries with one
+ *            address the FIRST wins (the reference scans its interfaces ascending and stops).
+ *   if_ips   InterfaceManager::get_interface_ip(egress_if): the interface's ip_configurations[0]. Of two
+ *            entries with one interface the first wins.
+ *   ports_up the ports p < num_ports with is_port_link_up(p): send_control_plane_packet's test
+ *            (switch.hpp:143). num_ports above NFCS_L2_MAX_PORTS: NFCS_EINVAL; a listed port >= num_ports is
+ *            ignored (it can never send).
+ * Setters, commit and upload behave exactly as in nfcs_fdb: a setter copies its input (NULL with n > 0:
+ * NFCS_EINVAL) and invalidates an earlier commit, so nfcs_icmp_respond_host returns NFCS_EINVAL until the
+ * next nfcs_icmp_commit; it does NOT invalidate an earlier upload, so nfcs_icmp_respond_device keeps serving
+ * the tables of the last nfcs_icmp_upload. The icmp must be destroyed before the ctx.
+ * Routes, ARP and interface MACs come from the nfcs_fib given to the call (uploaded to the same ctx). */
+typedef struct nfcs_icmp nfcs_icmp;
+typedef struct nfcs_icmp_local { uint32_t ip; uint8_t mac[6]; uint8_t pad[2]; } nfcs_icmp_local;
+typedef struct nfcs_icmp_if_ip { uint32_t egress_if; uint32_t ip; } nfcs_icmp_if_ip;
+#ifdef __cplusplus
+static_assert(sizeof(nfcs_icmp_local) == 12, "nfcs_icmp_local is a 12-byte record");
+static_assert(sizeof(nfcs_icmp_if_ip) == 8, "nfcs_icmp_if_ip is an 8-byte record");
+#endif
+NFCS_API int nfcs_icmp_create(nfcs_icmp** out);
+NFCS_API int nfcs_icmp_destroy(nfcs_icmp* icmp); /* also frees what nfcs_icmp_upload allocated */
+NFCS_API int nfcs_icmp_set_local(nfcs_icmp* icmp, const nfcs_icmp_local* local, uint32_t n);
+NFCS_API int nfcs_icmp_set_if_ips(nfcs_icmp* icmp, const nfcs_icmp_if_ip* if_ips, uint32_t n);
+NFCS_API int nfcs_icmp_set_ports_up(nfcs_icmp* icmp, const uint32_t* ports, uint32_t n, uint32_t num_ports);
+NFCS_API int nfcs_icmp_commit(nfcs_icmp* icmp);
+/* Copies the committed tables to ctx's device (synchronous; replaces an earlier upload, which must no
+ * longer be in use). NFCS_EINVAL before nfcs_icmp_commit. */
+NFCS_API int nfcs_icmp_upload(nfcs_ctx* ctx, nfcs_icmp* icmp);
+
+/* Route -> next hop -> ARP -> interface MAC for one address from the committed FIB, WITHOUT the is_my_ip and
+ * TTL steps of nfcs_fib_lookup_host: what send_icmp_error_packet_base does for the original's source address
+ * (icmp_processor.cpp:212-251). *verdict = NFCS_RT_FORWARD, NFCS_RT_NO_ROUTE, NFCS_RT_ARP_MISS or
+ * NFCS_RT_NO_IF_MAC only; *nh = the next-hop index for NFCS_RT_FORWARD, else NFCS_NH_NONE; *egress_if = the
+ * first matching route's interface WHENEVER a route matches (also for ARP_MISS and NO_IF_MAC: the ICMP stage
+ * tests the interface's address before ARP), NFCS_IF_NONE for NFCS_RT_NO_ROUTE (each may be NULL). Wherever
+ * nfcs_fib_lookup_host decides neither LOCAL nor TTL_EXPIRED its verdict and nh are these. NFCS_EINVAL before
+ * nfcs_fib_commit. The kernels of this section call the device form of the same function. */
+NFCS_API int nfcs_fib_resolve_host(const nfcs_fib* fib, uint32_t ip, uint32_t* verdict, uint32_t* nh,
+                                   uint32_t* egress_if);
+
+/* What became of source packet i (d_status). */
+enum {
+    NFCS_ICMP_ST_NONE = 0,           /* the verdict is none of the three, the packet is not live, or it fails the
+                                        lookup's IPv4 predicate (a verdict the lookup would not have given)      */
+    NFCS_ICMP_ST_ECHO_REPLY = 1,     /* message emitted                                                        */
+    NFCS_ICMP_ST_TIME_EXCEEDED = 2,  /* message emitted (11/0)                                                 */
+    NFCS_ICMP_ST_UNREACHABLE = 3,    /* message emitted (3/0)                                                  */
+    NFCS_ICMP_ST_TO_CPU = 4,         /* local, not ICMP: packet_handler_'s (switch.hpp:273-275)                */
+    NFCS_ICMP_ST_IGNORED = 5,        /* local ICMP that is not an answerable echo request: icmp() null, not type
+                                        8 code 0, or total_length < ihl*4 + 8                                  */
+    NFCS_ICMP_ST_NO_LOCAL_MAC = 6,   /* echo request, no `local` entry for the destination (lines 55-59)       */
+    NFCS_ICMP_ST_SRC_NO_ROUTE = 7,   /* error: the original's source has no route (213-219)                    */
+    NFCS_ICMP_ST_SRC_NO_IF_IP = 8,   /* error: the route's interface has no address (222-227)                  */
+    NFCS_ICMP_ST_SRC_ARP_MISS = 9,   /* error: no ARP entry for the next hop (236-242); the reference sends an
+                                        ARP request here, which stays the caller's                             */
+    NFCS_ICMP_ST_SRC_NO_IF_MAC = 10, /* error: the route's interface has no MAC (245-250)                      */
+    NFCS_ICMP_ST_PORT_DOWN = 11,     /* built, then dropped by send_control_plane_packet: port >= num_ports or
+                                        not up. Not emitted.                                                   */
+    NFCS_ICMP_ST_OOB = 12,           /* DEVIATION: an error's original with l2 + ihl*4 > len (the reference
+                                        copies past its buffer). No message.                                   */
+    NFCS_ICMP_ST_TOO_LONG = 13,      /* DEVIATION: a reply with 28 + payload > 65535 (the reference truncates
+                                        total_length to 16 bits). No message.                                  */
+    NFCS_ICMP_ST_OVERFLOW = 14       /* a message was called for and cap or the region ran out                 */
+};
+
+/* Rules (the overflow, padding and live conventions are nfcs_flood_expand_device's).
+ * Region and descriptors
+ *  - A source packet is LIVE when off16*16 + round_up(len, 16) <= msg_base (msg_base <= arena_bytes, else
+ *    NFCS_EINVAL). A source that is not live produces nothing; no source frame can overlap a message.
+ *  - Messages are numbered in source-packet order (a packet yields at most one). Message slots are laid out in
+ *    that order from msg_base, each round_up(msg_len, msg_align) bytes. msg_align is a power of two >= 16 and
+ *    msg_base a multiple of it; anything else is NFCS_EINVAL.
+ *  - d_msg_desc[k] describes message k, d_msg_src[k] is its source packet, d_msg_port[k] the port
+ *    send_control_plane_packet is called with. A message's bytes [msg_len, round_up(msg_len, 16)) are written
+ *    zero; the rest of its slot is not written.
+ *  - Message k is emitted iff k < cap and the region used up to and including message k ends at or before
+ *    arena_bytes. Both are prefix conditions: the emitted messages are the first `messages` of the full list.
+ *    The sources of the others read NFCS_ICMP_ST_OVERFLOW. messages_needed and msg_bytes_needed say what the
+ *    burst called for.
+ *  - Entries [messages, cap) are written inert: desc {0, 0}, port NFCS_IF_NONE, src NFCS_ITEM_NONE.
+ *  - Nothing is written outside [msg_base, arena_bytes) or the first cap entries, ever.
+ *  - n == 0: NFCS_OK, no launch, nothing written. cap == 0 lets the three message arrays be NULL.
+ * Echo reply (d_rt_verdict[i] == NFCS_RT_LOCAL; ONE ingress port per call, as in nfcs_l2_lookup_device)
+ *  - The request qualifies when protocol is 1; icmp() is present (l2 + ihl*4 + 8 <= len, l2 = 18 behind one
+ *    0x8100 tag, else 14); type is 8 and code 0; a `local` entry exists for the destination; and
+ *    total_length >= ihl*4 + 8.
+ *  - payload = total_length - ihl*4 - 8, or 0 when l2 + ihl*4 + 8 + payload > len (lines 117-122).
+ *  - The message is 42 + payload bytes (lines 136-173): Ethernet source = the local entry's MAC, destination =
+ *    the request's source MAC, EtherType 0x0800, untagged also for a tagged request; IPv4 45 00, total length,
+ *    id 0, no fragment, TTL 64, protocol 1, addresses swapped; ICMP type 0 code 0, identifier and sequence
+ *    number copied, payload copied. Port = ingress_port.
+ * Errors (NFCS_RT_TTL_EXPIRED -> 11/0, NFCS_RT_NO_ROUTE -> 3/0), checks in the reference's order
+ *  - nfcs_fib_resolve_host on the original's source address: no route; then no if_ip for the route's
+ *    interface; then ARP miss; then no interface MAC.
+ *  - copied = ihl*4 + min(8, len - (l2 + ihl*4)) (lines 255-265; IHL < 5 as written there).
+ *  - The message is 42 + copied bytes: MACs from the resolved next hop; IPv4 id = d_ip_id[i] (0 when d_ip_id
+ *    is NULL; the reference draws rand()), TTL 64, source = the interface's first address, destination = the
+ *    original's source; ICMP with 4 zero bytes behind the checksum, then the original's IPv4 header and L4
+ *    bytes. Port = the route's interface.
+ * Both kinds
+ *  - A message whose port is >= num_ports or not up is dropped by send_control_plane_packet after it was
+ *    built: it is not emitted and takes no slot (NFCS_ICMP_ST_PORT_DOWN).
+ *  - Both checksums are what update_checksums() writes on the built message (lines 180, 336), the odd-length
+ *    low-byte rule and the 0 / 0xFFFF cases included, computed from the message's own bytes in the pass that
+ *    builds it: nothing is derived from the request's checksum, which may be wrong.
+ * Downstream
+ *  - The messages are untagged: nfcs_egress_plan_device(.., d_msg_desc, m, NULL, NULL, d_msg_port, ..) returns
+ *    NFCS_VLAN_NOP for all of them and the queue is enqueue_packet's classification. The caller goes straight
+ *    to nfcs_egress_enqueue_device and the append: no VLAN edit and no egress ACL, as
+ *    send_control_plane_packet does.
+ *  - ORDER, the one difference: within one (port, queue) the reference interleaves messages with data packets
+ *    by source packet. Two lists (the flood stage's items, then these messages) enqueue the data packets
+ *    first. Within the message list the order is the reference's.
+ *  - Scratch (one 24-byte record per tile of NFCS_ICMP_TILE_PKTS packets) belongs to the context, grows on
+ *    demand and is freed by nfcs_ctx_destroy; a failed allocation returns NFCS_ENOMEM and leaves the context
+ *    usable, as the flood stage does. */
+#define NFCS_ICMP_TILE_PKTS 1024u /* packets per scan tile; SPEED ONLY, tests place sizes around it */
+
+typedef struct nfcs_icmp_totals {
+    uint32_t messages;        /* emitted: entries [0, messages) of the message arrays are valid        */
+    uint32_t messages_needed; /* what the burst calls for; > messages means cap or the region ran out  */
+    uint32_t echo_replies;    /* emitted messages that are echo replies                                 */
+    uint32_t errors;          /* emitted messages that are 11/0 or 3/0                                  */
+    uint64_t msg_bytes;       /* bytes of the message region the emitted messages occupy (slots)        */
+    uint64_t msg_bytes_needed;
+} nfcs_icmp_totals;
+#ifdef __cplusplus
+static_assert(sizeof(nfcs_icmp_totals) == 32, "nfcs_icmp_totals is a 32-byte record");
+#endif
+
+/* d_arena 16-byte aligned; d_desc and d_rt_verdict (n bytes, required) as the lookup wrote them; d_ip_id
+ * optional (NULL) n u16 in host order; d_msg_desc (8-byte aligned), d_msg_port, d_msg_src: cap entries each;
+ * d_status optional (NULL) n bytes NFCS_ICMP_ST_*; d_totals: one record, 8-byte aligned. icmp and fib must be
+ * uploaded to ctx and stay unchanged until the call completes. Asynchronous on the stream. Launches (speed
+ * only): classify + size per tile, a scan of the tile sums, emit + build per tile, padding. */
+NFCS_API int nfcs_icmp_respond_device(nfcs_ctx* ctx, const nfcs_icmp* icmp, const nfcs_fib* fib, uint32_t ingress_port,
+                                      uint8_t* d_arena, uint64_t arena_bytes, uint64_t msg_base, uint32_t msg_align,
+                                      const nfcs_desc* d_desc, uint32_t n, const uint8_t* d_rt_verdict,
+                                      const uint16_t* d_ip_id, uint32_t cap, nfcs_desc* d_msg_desc, uint32_t* d_msg_port,
+                                      uint32_t* d_msg_src, uint8_t* d_status, nfcs_icmp_totals* d_totals, void* stream);
+/* The same sequential walk on the CPU (host arrays, same meanings): the definition the kernels equal bit for
+ * bit. It takes the arena and writes the messages into it. icmp and fib must be committed. */
+NFCS_API int nfcs_icmp_respond_host(const nfcs_icmp* icmp, const nfcs_fib* fib, uint32_t ingress_port, uint8_t* arena,
+                                    uint64_t arena_bytes, uint64_t msg_base, uint32_t msg_align, const nfcs_desc* desc,
+                                    uint32_t n, const uint8_t* rt_verdict, const uint16_t* ip_id, uint32_t cap,
+                                    nfcs_desc* msg_desc, uint32_t* msg_port, uint32_t* msg_src, uint8_t* status,
+                                    nfcs_icmp_totals* totals);
+
 /* ---- VLAN push / pop + checksum ---------------------------------------- */
 
 /* One VLAN edit per packet as a u32: the operation in bits 30-31, the priority in bits 13-15

@@ -84,6 +84,17 @@ FLOOD_TOTALS_DTYPE = np.dtype([("items", "<u4"), ("items_needed", "<u4"), ("copi
                                ("copy_bytes", "<u8"), ("copy_bytes_needed", "<u8")])
 assert FLOOD_TOTALS_DTYPE.itemsize == 32
 
+# the ICMP responder (include/nfcs.h nfcs_icmp_*, NFCS_ICMP_ST_*)
+ICMP_TILE_PKTS = 1024  # NFCS_ICMP_TILE_PKTS: the scan's tile, speed only
+(ICMP_ST_NONE, ICMP_ST_ECHO_REPLY, ICMP_ST_TIME_EXCEEDED, ICMP_ST_UNREACHABLE, ICMP_ST_TO_CPU, ICMP_ST_IGNORED,
+ ICMP_ST_NO_LOCAL_MAC, ICMP_ST_SRC_NO_ROUTE, ICMP_ST_SRC_NO_IF_IP, ICMP_ST_SRC_ARP_MISS, ICMP_ST_SRC_NO_IF_MAC,
+ ICMP_ST_PORT_DOWN, ICMP_ST_OOB, ICMP_ST_TOO_LONG, ICMP_ST_OVERFLOW) = range(15)
+ICMP_LOCAL_DTYPE = np.dtype([("ip", "<u4"), ("mac", "u1", (6,)), ("pad", "u1", (2,))])
+ICMP_IF_IP_DTYPE = np.dtype([("egress_if", "<u4"), ("ip", "<u4")])
+ICMP_TOTALS_DTYPE = np.dtype([("messages", "<u4"), ("messages_needed", "<u4"), ("echo_replies", "<u4"),
+                              ("errors", "<u4"), ("msg_bytes", "<u8"), ("msg_bytes_needed", "<u8")])
+assert ICMP_LOCAL_DTYPE.itemsize == 12 and ICMP_IF_IP_DTYPE.itemsize == 8 and ICMP_TOTALS_DTYPE.itemsize == 32
+
 # the egress stage (include/nfcs.h nfcs_egress_*, NFCS_EQ_*)
 QOS_MAX_QUEUES = 8      # classify_packet_to_queue names at most 8 queues from 8 PCP values
 QUEUE_NONE = 0xFF
@@ -218,6 +229,19 @@ def _declare(L):
         "nfcs_flood_expand_device": ([_vp, _vp, _u32, _u32, _vp, _u64, _u64, _u32, _vp, _u32] + [_vp] * 5 + [_u32] +
                                      [_vp] * 5, ctypes.c_int),
         "nfcs_flood_expand_host": ([_vp, _u32, _u32, _u64, _u64, _u32, _vp, _u32] + [_vp] * 5 + [_u32] + [_vp] * 4,
+                                   ctypes.c_int),
+        "nfcs_icmp_create": ([ctypes.POINTER(_vp)], ctypes.c_int),
+        "nfcs_icmp_destroy": ([_vp], ctypes.c_int),
+        "nfcs_icmp_set_local": ([_vp, _vp, _u32], ctypes.c_int),
+        "nfcs_icmp_set_if_ips": ([_vp, _vp, _u32], ctypes.c_int),
+        "nfcs_icmp_set_ports_up": ([_vp, _vp, _u32, _u32], ctypes.c_int),
+        "nfcs_icmp_commit": ([_vp], ctypes.c_int),
+        "nfcs_icmp_upload": ([_vp, _vp], ctypes.c_int),
+        "nfcs_fib_resolve_host": ([_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32)],
+                                  ctypes.c_int),
+        "nfcs_icmp_respond_device": ([_vp, _vp, _vp, _u32, _vp, _u64, _u64, _u32, _vp, _u32, _vp, _vp, _u32] +
+                                     [_vp] * 6, ctypes.c_int),
+        "nfcs_icmp_respond_host": ([_vp, _vp, _u32, _vp, _u64, _u64, _u32, _vp, _u32, _vp, _vp, _u32] + [_vp] * 5,
                                    ctypes.c_int),
         "nfcs_egress_create": ([ctypes.POINTER(_vp)], ctypes.c_int),
         "nfcs_egress_destroy": ([_vp], ctypes.c_int),
@@ -373,6 +397,15 @@ class Fib:
         v, h, e = _u32(), _u32(), _u32()
         _check(lib().nfcs_fib_lookup_host(self.ptr, int(dst_ip), int(ttl), ctypes.byref(v), ctypes.byref(h),
                                           ctypes.byref(e)), "nfcs_fib_lookup_host")
+        return int(v.value), int(h.value), int(e.value)
+
+    def resolve_host(self, ip: int) -> tuple[int, int, int]:
+        """(verdict, next-hop index, the matching route's interface) for one address WITHOUT the is_my_ip and
+        TTL steps (nfcs_fib_resolve_host): RT_FORWARD / RT_NO_ROUTE / RT_ARP_MISS / RT_NO_IF_MAC only; the
+        interface is given whenever a route matches."""
+        v, h, e = _u32(), _u32(), _u32()
+        _check(lib().nfcs_fib_resolve_host(self.ptr, int(ip), ctypes.byref(v), ctypes.byref(h), ctypes.byref(e)),
+               "nfcs_fib_resolve_host")
         return int(v.value), int(h.value), int(e.value)
 
     def close(self):
@@ -638,6 +671,89 @@ class Fdb:
     def close(self):
         if getattr(self, "ptr", None):
             lib().nfcs_fdb_destroy(self.ptr)
+            self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Icmp:
+    """The tables behind Engine.icmp_respond_device (nfcs_icmp): the switch's own addresses with their MACs
+    (get_mac_for_ip), each interface's first address (get_interface_ip) and the ports that are up
+    (send_control_plane_packet's test). Addresses are u32 in network byte order, as in Fib; of duplicates the
+    first wins. Routes, ARP and interface MACs come from the Fib given to the call."""
+
+    def __init__(self):
+        p = _vp()
+        _check(lib().nfcs_icmp_create(ctypes.byref(p)), "nfcs_icmp_create")
+        self.ptr = p.value
+
+    def set_local(self, local):
+        """ICMP_LOCAL_DTYPE records {ip, mac}."""
+        local = np.ascontiguousarray(local, dtype=ICMP_LOCAL_DTYPE)
+        _check(lib().nfcs_icmp_set_local(self.ptr, local.ctypes.data if len(local) else None, len(local)),
+               "nfcs_icmp_set_local")
+        return self
+
+    def set_if_ips(self, if_ips):
+        """ICMP_IF_IP_DTYPE records {egress_if, ip}."""
+        if_ips = np.ascontiguousarray(if_ips, dtype=ICMP_IF_IP_DTYPE)
+        _check(lib().nfcs_icmp_set_if_ips(self.ptr, if_ips.ctypes.data if len(if_ips) else None, len(if_ips)),
+               "nfcs_icmp_set_if_ips")
+        return self
+
+    def set_ports_up(self, ports, num_ports: int):
+        """The ports below num_ports whose link is up."""
+        ports = np.ascontiguousarray(ports, dtype=np.uint32)
+        _check(lib().nfcs_icmp_set_ports_up(self.ptr, ports.ctypes.data if len(ports) else None, len(ports),
+                                            int(num_ports)), "nfcs_icmp_set_ports_up")
+        return self
+
+    def commit(self):
+        _check(lib().nfcs_icmp_commit(self.ptr), "nfcs_icmp_commit")
+        return self
+
+    def upload(self, engine: "Engine"):
+        """Copy the committed tables to the engine's device; close the Icmp before the engine."""
+        _check(lib().nfcs_icmp_upload(engine.ctx, self.ptr), "nfcs_icmp_upload")
+        return self
+
+    def respond_host(self, fib: "Fib", ingress_port: int, arena, msg_base: int, msg_align: int, desc, rt_verdict,
+                     cap: int, ip_id=None) -> dict:
+        """The sequential walk behind Engine.icmp_respond_device, on the CPU (nfcs_icmp_respond_host): builds
+        the burst's echo replies and TTL / unreachable errors into arena[msg_base:] IN PLACE (arena: a writable
+        contiguous uint8 array) and returns msg_desc (cap DESC_DTYPE), msg_port and msg_src (cap u32 each; the
+        entries past totals["messages"] are inert), status (n bytes ICMP_ST_*) and totals (one
+        ICMP_TOTALS_DTYPE record)."""
+        assert arena.dtype == np.uint8 and arena.flags.c_contiguous and arena.flags.writeable
+        desc = np.ascontiguousarray(desc, dtype=DESC_DTYPE)
+        n = len(desc)
+        rt_verdict = np.ascontiguousarray(rt_verdict, dtype=np.uint8)
+        ip_id = None if ip_id is None else np.ascontiguousarray(ip_id, dtype=np.uint16)
+        if len(rt_verdict) != n or (ip_id is not None and len(ip_id) != n):
+            raise NfcsError("respond_host: every per-packet array needs n entries")
+        msg_desc, msg_port = np.zeros(cap, DESC_DTYPE), np.zeros(cap, np.uint32)
+        msg_src, totals = np.zeros(cap, np.uint32), np.zeros(1, ICMP_TOTALS_DTYPE)
+        status = np.zeros(n, np.uint8)
+        dp = lambda a: a.ctypes.data if a is not None and len(a) else None
+        _check(lib().nfcs_icmp_respond_host(self.ptr, fib.ptr, int(ingress_port), arena.ctypes.data, arena.nbytes,
+                                            int(msg_base), int(msg_align), dp(desc), n, dp(rt_verdict), dp(ip_id),
+                                            int(cap), dp(msg_desc), dp(msg_port), dp(msg_src), dp(status),
+                                            totals.ctypes.data), "nfcs_icmp_respond_host")
+        return {"msg_desc": msg_desc, "msg_port": msg_port, "msg_src": msg_src, "status": status, "totals": totals[0]}
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            lib().nfcs_icmp_destroy(self.ptr)
             self.ptr = None
 
     def __enter__(self):
@@ -1069,6 +1185,22 @@ class Engine:
                                               ptr(fwd_status), ptr(l2_port), ptr(l2_verdict), ptr(l2_vlan), cap,
                                               ptr(item_desc), ptr(item_port), ptr(item_src), ptr(totals), stream),
                "nfcs_flood_expand_device")
+
+    def icmp_respond_device(self, icmp: "Icmp", fib: Fib, ingress_port: int, arena, arena_bytes: int, msg_base: int,
+                            msg_align: int, desc, n: int, rt_verdict, cap: int, msg_desc, msg_port, msg_src, totals,
+                            ip_id=None, status=None, stream=None):
+        """The burst's ICMP answers built on the device (nfcs_icmp_respond_device): per live packet whose
+        rt_verdict (n bytes of route_lookup_device) is RT_LOCAL an echo reply where it is an answerable echo
+        request, per RT_TTL_EXPIRED / RT_NO_ROUTE packet an ICMP 11/0 / 3/0 error, checksums included, in the
+        region [msg_base, arena_bytes) of the same arena in slots of round_up(msg_len, msg_align). msg_desc (cap
+        DESC_DTYPE), msg_port, msg_src (cap u32 each) and totals (one ICMP_TOTALS_DTYPE record) are device
+        buffers; entries past totals.messages are written inert. ip_id (n u16: the errors' IPv4 ids) and status
+        (n bytes ICMP_ST_*) optional. Plan and enqueue then run over msg_desc / msg_port."""
+        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
+        _check(lib().nfcs_icmp_respond_device(self.ctx, icmp.ptr, fib.ptr, int(ingress_port), ptr(arena), arena_bytes,
+                                              msg_base, msg_align, ptr(desc), n, ptr(rt_verdict), ptr(ip_id), cap,
+                                              ptr(msg_desc), ptr(msg_port), ptr(msg_src), ptr(status), ptr(totals),
+                                              stream), "nfcs_icmp_respond_device")
 
     def egress_plan_device(self, egress: "Egress", arena, arena_bytes: int, desc, n: int, port, ops, queue,
                            l3_port=None, fwd_status=None, l2_port=None, stream=None):

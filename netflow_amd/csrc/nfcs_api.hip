@@ -1511,6 +1511,180 @@ NFCS_API int nfcs_flood_expand_device(nfcs_ctx* c, const nfcs_fdb* f, uint32_t i
     return NFCS_OK;
 }
 
+// ---- ICMP responder (nfcs_icmp.h: compile, the plan, the host walk) and its kernels -----------------
+}  // extern "C"
+
+struct nfcs_icmp {
+    nfcs::IcmpInputs in;
+    nfcs::IcmpTables t;
+    bool committed = false;
+    // nfcs_icmp_upload: one device allocation holding every array, on `device`
+    int device = -1;
+    uint8_t* d_blob = nullptr;
+    nfcs::IcmpView dev{};
+    bool uploaded = false;
+};
+
+namespace {
+void icmp_drop_upload(nfcs_icmp* m) {
+    if (m->d_blob) {
+        DeviceGuard dg_(m->device);
+        if (dg_.err == hipSuccess) (void)hipFree(m->d_blob);
+    }
+    m->d_blob = nullptr;
+    m->dev = nfcs::IcmpView{};
+    m->uploaded = false;
+}
+template <class T>
+int icmp_set(nfcs_icmp* m, std::vector<T>& dst, const T* src, uint32_t n) {
+    if (!m || (n > 0 && !src)) return NFCS_EINVAL;
+    try {
+        dst.assign(src, src + n);
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+    m->committed = false;  // the device copy, if any, stays as it is until the next upload
+    return NFCS_OK;
+}
+nfcs::FibView fib_dev_view(const nfcs_fib* f) {
+    return nfcs::FibView{(const nfcs::U2*)f->dev.rt_nm, (const nfcs::U2*)f->dev.rt_info, f->dev.routes_padded,
+                         f->dev.arp_ip, f->dev.arp_nh, f->dev.arps, f->d_table};
+}
+}  // namespace
+
+extern "C" {
+
+NFCS_API int nfcs_icmp_create(nfcs_icmp** out) {
+    if (!out) return NFCS_EINVAL;
+    *out = new (std::nothrow) nfcs_icmp();
+    return *out ? NFCS_OK : NFCS_ENOMEM;
+}
+
+NFCS_API int nfcs_icmp_destroy(nfcs_icmp* m) {
+    if (!m) return NFCS_EINVAL;
+    icmp_drop_upload(m);
+    delete m;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_icmp_set_local(nfcs_icmp* m, const nfcs_icmp_local* local, uint32_t n) {
+    return m ? icmp_set(m, m->in.local, local, n) : NFCS_EINVAL;
+}
+NFCS_API int nfcs_icmp_set_if_ips(nfcs_icmp* m, const nfcs_icmp_if_ip* if_ips, uint32_t n) {
+    return m ? icmp_set(m, m->in.if_ips, if_ips, n) : NFCS_EINVAL;
+}
+NFCS_API int nfcs_icmp_set_ports_up(nfcs_icmp* m, const uint32_t* ports, uint32_t n, uint32_t num_ports) {
+    if (!m || num_ports > nfcs::kIcmpMaxPorts) return NFCS_EINVAL;
+    const int rc = icmp_set(m, m->in.up, ports, n);
+    if (rc == NFCS_OK) m->in.num_ports = num_ports;
+    return rc;
+}
+
+NFCS_API int nfcs_icmp_commit(nfcs_icmp* m) {
+    if (!m) return NFCS_EINVAL;
+    try {
+        nfcs::icmp_compile(m->in, m->t);
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+    m->committed = true;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_icmp_upload(nfcs_ctx* c, nfcs_icmp* m) {
+    if (!c || !m || !m->committed) return NFCS_EINVAL;
+    icmp_drop_upload(m);
+    DeviceGuard dg_(c->di.device);
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    const nfcs::IcmpTables& t = m->t;
+    // one blob, every array on a 16-byte boundary
+    auto up16 = [](size_t x) { return (x + 15u) & ~size_t(15); };
+    const size_t o_lip = 0, o_lmac = o_lip + up16(t.local_ip.size() * 4u), o_iid = o_lmac + up16(t.local_mac.size() * 8u);
+    const size_t o_iip = o_iid + up16(t.if_id.size() * 4u), o_up = o_iip + up16(t.if_ip.size() * 4u);
+    const size_t total = o_up + up16(t.up.size() * 4u);
+    std::vector<uint8_t> blob(total + 16u, 0);
+    auto put = [&](size_t o, const void* p, size_t bytes) {
+        if (bytes) memcpy(blob.data() + o, p, bytes);
+    };
+    put(o_lip, t.local_ip.data(), t.local_ip.size() * 4u);
+    put(o_lmac, t.local_mac.data(), t.local_mac.size() * 8u);
+    put(o_iid, t.if_id.data(), t.if_id.size() * 4u);
+    put(o_iip, t.if_ip.data(), t.if_ip.size() * 4u);
+    put(o_up, t.up.data(), t.up.size() * 4u);
+    NFCS_HIP(hipMalloc(&m->d_blob, blob.size()));
+    m->device = c->di.device;
+    const hipError_t e = hipMemcpy(m->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        icmp_drop_upload(m);
+        return hip_fail(e);
+    }
+    m->dev = nfcs::IcmpView{(const uint32_t*)(m->d_blob + o_lip), (const nfcs::U2*)(m->d_blob + o_lmac),
+                            (uint32_t)t.local_ip.size(), (const uint32_t*)(m->d_blob + o_iid),
+                            (const uint32_t*)(m->d_blob + o_iip), (uint32_t)t.if_id.size(),
+                            (const uint32_t*)(m->d_blob + o_up), t.num_ports};
+    m->uploaded = true;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_fib_resolve_host(const nfcs_fib* f, uint32_t ip, uint32_t* verdict, uint32_t* nh, uint32_t* egress_if) {
+    if (!f || !f->committed) return NFCS_EINVAL;
+    uint32_t v, h, e;
+    nfcs::fib_resolve(nfcs::fib_view(f->t), ip, &v, &h, &e);
+    if (verdict) *verdict = v;
+    if (nh) *nh = h;
+    if (egress_if) *egress_if = e;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_icmp_respond_host(const nfcs_icmp* m, const nfcs_fib* f, uint32_t ingress_port, uint8_t* arena,
+                                    uint64_t arena_bytes, uint64_t msg_base, uint32_t msg_align, const nfcs_desc* desc,
+                                    uint32_t n, const uint8_t* rt_verdict, const uint16_t* ip_id, uint32_t cap,
+                                    nfcs_desc* msg_desc, uint32_t* msg_port, uint32_t* msg_src, uint8_t* status,
+                                    nfcs_icmp_totals* totals) {
+    if (!m || !m->committed || !f || !f->committed) return NFCS_EINVAL;
+    if (!nfcs::icmp_args_ok(arena_bytes, msg_base, msg_align)) return NFCS_EINVAL;
+    if (n == 0) return NFCS_OK;
+    if (!arena || !desc || !rt_verdict || !totals || (cap > 0 && (!msg_desc || !msg_port || !msg_src))) return NFCS_EINVAL;
+    try {
+        nfcs::icmp_respond(m->t, f->t, ingress_port, arena, arena_bytes, msg_base, msg_align, desc, n, rt_verdict, ip_id,
+                           cap, msg_desc, msg_port, msg_src, status, totals);
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_icmp_respond_device(nfcs_ctx* c, const nfcs_icmp* m, const nfcs_fib* f, uint32_t ingress_port,
+                                      uint8_t* d_arena, uint64_t arena_bytes, uint64_t msg_base, uint32_t msg_align,
+                                      const nfcs_desc* d_desc, uint32_t n, const uint8_t* d_rt_verdict,
+                                      const uint16_t* d_ip_id, uint32_t cap, nfcs_desc* d_msg_desc, uint32_t* d_msg_port,
+                                      uint32_t* d_msg_src, uint8_t* d_status, nfcs_icmp_totals* d_totals, void* stream) {
+    if (!c || !m || !m->uploaded || m->device != c->di.device) return NFCS_EINVAL;
+    if (!f || !f->uploaded || f->device != c->di.device) return NFCS_EINVAL;
+    if (!nfcs::icmp_args_ok(arena_bytes, msg_base, msg_align)) return NFCS_EINVAL;
+    DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    if (n == 0) return NFCS_OK;
+    if (!d_arena || !d_desc || !d_rt_verdict || !d_totals || ((uintptr_t)d_arena & 15u) || ((uintptr_t)d_totals & 7u))
+        return NFCS_EINVAL;
+    if (cap > 0 && (!d_msg_desc || !d_msg_port || !d_msg_src)) return NFCS_EINVAL;
+    if (((uintptr_t)d_ip_id & 1u) || ((uintptr_t)d_msg_desc & 7u) || ((uintptr_t)d_msg_port & 3u) ||
+        ((uintptr_t)d_msg_src & 3u))
+        return NFCS_EINVAL;
+    hipStream_t st = pick(c, stream);
+    hipError_t e = acquire_eq(c, nfcs::flood_scratch_words(n), st);  // the enqueue's scratch serves this stage too
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();  // the context stays usable: only this call's scratch is missing
+        return NFCS_ENOMEM;
+    }
+    NFCS_HIP(e);
+    const nfcs::IcmpArgs a{d_arena, arena_bytes, msg_base, msg_align, ingress_port, n, cap, d_desc, d_rt_verdict, d_ip_id,
+                           d_msg_desc, d_msg_port, d_msg_src, d_status, d_totals};
+    NFCS_HIP(nfcs::launch_icmp_respond(c->di, m->dev, fib_dev_view(f), a, c->eq_ws, st));
+    NFCS_HIP(release_eq(c, st));
+    return NFCS_OK;
+}
+
 // ---- Egress stage (nfcs_egress.h: compile, host plan, host enqueue) and its kernels ----------------
 }  // extern "C"
 

@@ -12,6 +12,12 @@
 
 #include "nfcs.h"
 
+#if defined(__HIPCC__)
+#define NFCS_HD __host__ __device__
+#else
+#define NFCS_HD
+#endif
+
 namespace nfcs {
 
 // What a route's word says (FibTables::rt_info[r].x): a next-hop index, or one of these.
@@ -45,7 +51,7 @@ struct FibInputs {
 };
 
 // Index of key in the ascending array a[0..n), or NFCS_NH_NONE. The kernel's search is the same loop.
-inline uint32_t fib_find(const uint32_t* a, uint32_t n, uint32_t key) {
+NFCS_HD inline uint32_t fib_find(const uint32_t* a, uint32_t n, uint32_t key) {
     uint32_t lo = 0, hi = n;
     while (lo < hi) {
         const uint32_t mid = lo + (hi - lo) / 2u;
@@ -120,6 +126,56 @@ inline void fib_compile(const FibInputs& in, FibTables& t) {
     }
 }
 
+// What a matching route says about one address: route word `word` (rt_info[r].x), the ARP arrays, the
+// address the route was matched for. FORWARD (with the next-hop index), ARP_MISS or NO_IF_MAC
+// (switch.hpp:285-292; icmp_processor.cpp:231-251 has the same two steps). Host and device, this one
+// definition: fib_decide, fib_resolve, route_lookup_kernel and the ICMP stage's kernels call it.
+NFCS_HD inline uint32_t fib_route_word(uint32_t word, const uint32_t* arp_ip, const uint32_t* arp_nh, uint32_t arps,
+                                       uint32_t ip, uint32_t* nh) {
+    *nh = NFCS_NH_NONE;
+    if (word == kRtGwArpMiss) return NFCS_RT_ARP_MISS;
+    if (word == kRtGwNoIfMac) return NFCS_RT_NO_IF_MAC;
+    if (word == kRtConnected) {  // ARP for the address itself
+        const uint32_t a = fib_find(arp_ip, arps, ip);
+        if (a == NFCS_NH_NONE) return NFCS_RT_ARP_MISS;
+        *nh = arp_nh[a];
+        return *nh == NFCS_NH_NONE ? (uint32_t)NFCS_RT_NO_IF_MAC : (uint32_t)NFCS_RT_FORWARD;
+    }
+    *nh = word;
+    return NFCS_RT_FORWARD;
+}
+
+// The compiled arrays as plain pointers: the host's vectors or the device copy of nfcs_fib_upload.
+struct FibView {
+    const U2* rt_nm;
+    const U2* rt_info;
+    uint32_t routes_padded;  // a multiple of kRtGroup; the padding pairs match nothing
+    const uint32_t* arp_ip;
+    const uint32_t* arp_nh;
+    uint32_t arps;
+    const nfcs_nexthop* table;
+};
+inline FibView fib_view(const FibTables& t) {
+    return FibView{t.rt_nm.data(), t.rt_info.data(), (uint32_t)t.rt_nm.size(), t.arp_ip.data(), t.arp_nh.data(),
+                   (uint32_t)t.arp_ip.size(), t.table.data()};
+}
+
+// Route -> next hop -> ARP -> interface MAC for one address, without fib_decide's is_my_ip and TTL steps
+// (nfcs_fib_resolve_host; the source address of an ICMP error, icmp_processor.cpp:212-251). *verdict is
+// FORWARD, NO_ROUTE, ARP_MISS or NO_IF_MAC; *egress_if is the first matching route's interface whenever a
+// route matches, whatever the verdict (the ICMP stage tests the interface's address before ARP).
+NFCS_HD inline void fib_resolve(const FibView& t, uint32_t ip, uint32_t* verdict, uint32_t* nh, uint32_t* egress_if) {
+    uint32_t r = NFCS_NH_NONE;
+    for (uint32_t i = 0; i < t.routes_padded && r == NFCS_NH_NONE; ++i)
+        if ((ip & t.rt_nm[i].y) == t.rt_nm[i].x) r = i;
+    *verdict = NFCS_RT_NO_ROUTE;
+    *nh = NFCS_NH_NONE;
+    *egress_if = NFCS_IF_NONE;
+    if (r == NFCS_NH_NONE) return;
+    *egress_if = t.rt_info[r].y;
+    *verdict = fib_route_word(t.rt_info[r].x, t.arp_ip, t.arp_nh, t.arps, ip, nh);
+}
+
 // The decision after the header predicate (switch.hpp:270-301) for one destination and TTL.
 inline void fib_decide(const FibTables& t, uint32_t dst, uint32_t ttl, uint32_t* verdict, uint32_t* nh,
                        uint32_t* egress_if) {
@@ -130,15 +186,7 @@ inline void fib_decide(const FibTables& t, uint32_t dst, uint32_t ttl, uint32_t*
         const uint32_t r = fib_first_route(t, dst);
         if (r == NFCS_NH_NONE) v = NFCS_RT_NO_ROUTE;
         else {
-            const uint32_t word = t.rt_info[r].x;
-            if (word == kRtGwArpMiss) v = NFCS_RT_ARP_MISS;
-            else if (word == kRtGwNoIfMac) v = NFCS_RT_NO_IF_MAC;
-            else if (word == kRtConnected) {
-                const uint32_t a = fib_find(t.arp_ip.data(), (uint32_t)t.arp_ip.size(), dst);
-                if (a == NFCS_NH_NONE) v = NFCS_RT_ARP_MISS;
-                else if (t.arp_nh[a] == NFCS_NH_NONE) v = NFCS_RT_NO_IF_MAC;
-                else { v = NFCS_RT_FORWARD; h = t.arp_nh[a]; }
-            } else { v = NFCS_RT_FORWARD; h = word; }
+            v = fib_route_word(t.rt_info[r].x, t.arp_ip.data(), t.arp_nh.data(), (uint32_t)t.arp_ip.size(), dst, &h);
             if (v == NFCS_RT_FORWARD) e = t.rt_info[r].y;
         }
     }

@@ -11,6 +11,7 @@
 #include "nfcs_egress.h"
 #include "nfcs_fdb.h"
 #include "nfcs_fib.h"
+#include "nfcs_icmp.h"
 #include "nfcs_txq.h"
 
 namespace nfcs {
@@ -324,6 +325,27 @@ struct FloodArgs {
 };
 hipError_t launch_flood_expand(const DevInfo& di, const FdbDev& fdb, const FloodArgs& a, uint32_t* scratch,
                                hipStream_t stream);
+
+// The ICMP responder: the flood stage's shape. Tiles of kIcmpTile consecutive packets, one
+// 1,024-thread workgroup each, one lane per packet; scratch as the flood's (one FloodSum per tile and one for
+// the totals: items = messages, copies = echo replies, bytes = slot bytes).
+constexpr uint32_t kIcmpTile = NFCS_ICMP_TILE_PKTS;
+static_assert(kIcmpTile == kFloodTile, "the scan and its scratch are the flood stage's");
+struct IcmpArgs {
+    uint8_t* arena;
+    uint64_t arena_bytes, msg_base;
+    uint32_t msg_align, ingress, n, cap;
+    const nfcs_desc* desc;
+    const uint8_t* rt_verdict;
+    const uint16_t* ip_id;
+    nfcs_desc* msg_desc;
+    uint32_t* msg_port;
+    uint32_t* msg_src;
+    uint8_t* status;
+    nfcs_icmp_totals* totals;
+};
+hipError_t launch_icmp_respond(const DevInfo& di, const IcmpView& icmp, const FibView& fib, const IcmpArgs& a,
+                               uint32_t* scratch, hipStream_t stream);
 
 hipError_t launch_gen_config(const DevInfo& di, int config, uint64_t seed, uint64_t first,
                              uint32_t n, uint8_t* arena, uint64_t arena_bytes,

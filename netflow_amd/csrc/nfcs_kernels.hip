@@ -2207,20 +2207,8 @@ __global__ __launch_bounds__(kBlock) void route_lookup_kernel(const nfcs_desc* _
     if (need) {
         v = NFCS_RT_NO_ROUTE;
         if (match != NFCS_NH_NONE) {  // match < fib.routes: the padding pairs match nothing
-            const uint2 info = fib.rt_info[match];
-            if (info.x == kRtGwArpMiss) v = NFCS_RT_ARP_MISS;
-            else if (info.x == kRtGwNoIfMac) v = NFCS_RT_NO_IF_MAC;
-            else if (info.x == kRtConnected) {  // ARP for the destination itself (285-286)
-                const uint32_t a = dev_find(fib.arp_ip, fib.arps, dst);
-                if (a == NFCS_NH_NONE) v = NFCS_RT_ARP_MISS;
-                else {
-                    nh = fib.arp_nh[a];
-                    v = nh == NFCS_NH_NONE ? (uint32_t)NFCS_RT_NO_IF_MAC : (uint32_t)NFCS_RT_FORWARD;
-                }
-            } else {
-                nh = info.x;
-                v = NFCS_RT_FORWARD;
-            }
+            const uint2 info = fib.rt_info[match];  // the gateway, or ARP for the destination itself (285-292)
+            v = fib_route_word(info.x, fib.arp_ip, fib.arp_nh, fib.arps, dst, &nh);
             if (v == NFCS_RT_FORWARD) eif = info.y;
         }
     }
@@ -3313,6 +3301,231 @@ hipError_t launch_flood_expand(const DevInfo& di, const FdbDev& fdb, const Flood
     if (a.cap) {
         const uint32_t g = (uint32_t)(((uint64_t)a.cap + kBlock - 1u) / kBlock);
         hipLaunchKernelGGL(flood_pad_kernel, dim3(g), dim3(kBlock), 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
+// ---- ICMP responder: echo replies and TTL / unreachable errors -------------------
+// nfcs_icmp.h icmp_respond is the sequential definition; these kernels equal it bit for bit. The flood stage's
+// shape, scan and scratch (FloodAcc: items = messages, copies = echo replies, bytes = slot bytes):
+//   1. icmp_count_kernel: per packet icmp_plan (nfcs_icmp.h, the host walk's function, on the frame's header
+//      bytes in device memory) -> (message?, echo?, slot bytes), summed over the tile into scratch[tile].
+//   2. flood_scan_kernel, as it is.
+//   3. icmp_emit_kernel: icmp_plan again, the tile's exclusive scan, and from the tile's prefix each packet's
+//      message index and slot offset; a packet yields at most one message, so "emitted" is one comparison per
+//      overflow condition. The packet's lane stores the list entry, the status byte and message chunks 0-1
+//      (bytes 0..31: MACs, EtherType, the IPv4 header up to its destination address, header checksum
+//      included: icmp_plan sums the header it built). The tile's messages are compacted into LDS and 64 rows
+//      of 16 lanes take them in turn: lane rl builds message chunks rl, rl + 16, ..., 6 per pass. Message byte
+//      b >= 44 is frame byte b + shift with shift a multiple of 4, so a chunk is ONE 16-byte load at a
+//      dword-aligned address (the dword shift is in the address; a pass issues its loads back to back, then
+//      repairs with dword loads the chunk whose load would leave the frame's 16-byte chunks), masked at the end, summed with v_sad_u16 as §3 does while it is in
+//      registers, and stored. The first pass's chunks stay in registers until the row's sum is complete:
+//      chunk 2 then takes the ICMP checksum and the pass is stored. Every message byte is written once and no
+//      byte of the region is read.
+//   4. icmp_pad_kernel: entries [messages, cap) inert.
+// No position comes from an atomic and no loop ends on data alone (a message has at most 4,097 chunks).
+constexpr uint32_t kIcmpR = 16, kIcmpK = 6;  // a row pass: 16 lanes x 6 chunks = 1,536 message bytes
+constexpr uint32_t kIcmpRows = kIcmpTile / kIcmpR;
+
+typedef uint32_t u32x4_a4_t __attribute__((ext_vector_type(4), aligned(4)));
+
+DEV IcmpPlan icmp_classify(const IcmpView& t, const FibView& fib, const IcmpArgs& a, uint64_t p, uint2* d) {
+    *d = make_uint2(0u, 0u);
+    if (p < a.n) {
+        *d = ((const uint2*)a.desc)[p];
+        const uint64_t off = (uint64_t)d->x * 16u;
+        if (off + flood_round_up(d->y, 16u) <= a.msg_base)  // live
+            return icmp_plan(t, fib, a.ingress, a.arena + off, d->y, a.rt_verdict[p], a.ip_id ? a.ip_id[p] : 0u);
+    }
+    IcmpPlan r;
+    r.status = NFCS_ICMP_ST_NONE;
+    r.msg_len = 0u;
+    r.port = NFCS_IF_NONE;
+    r.shift = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < kIcmpHdrDwords; ++i) r.hdr[i] = 0u;
+    return r;
+}
+DEV FloodAcc icmp_acc_of(const IcmpPlan& pl, uint32_t align) {
+    const uint32_t m = pl.msg_len ? 1u : 0u;
+    return FloodAcc{m, pl.status == NFCS_ICMP_ST_ECHO_REPLY ? m : 0u, 0u, m ? flood_round_up(pl.msg_len, align) : 0ull};
+}
+
+__global__ __launch_bounds__(kIcmpTile) void icmp_count_kernel(const IcmpView t, const FibView fib, const IcmpArgs a,
+                                                               uint32_t tiles, FloodSum* __restrict__ sums) {
+    __shared__ FloodAcc wsum[kFloodWaves];
+    const uint32_t tile = xcd_block_n(tiles);
+    uint2 d;
+    const IcmpPlan pl = icmp_classify(t, fib, a, (uint64_t)tile * kIcmpTile + threadIdx.x, &d);
+    FloodAcc total;
+    (void)flood_block_scan<kFloodWaves>(icmp_acc_of(pl, a.msg_align), wsum, &total);
+    if (threadIdx.x == 0) flood_store(sums + tile, total);
+}
+
+// Message chunk c >= 2 (bytes 16c .. 16c + 15, zero at and past len) in two steps, so that a row pass issues its
+// loads back to back: icmp_chunk_load, the one 16-byte load (from the zero line where the chunk does not exist or
+// the load would leave the frame's own 16-byte chunks), and icmp_chunk_finish, which repairs the latter case with
+// guarded dword loads, masks, puts the plan's bytes 32..43 into chunk 2 and adds the chunk's share of the ICMP sum
+// (message bytes 34.., as little-endian 16-bit words; an odd last byte counts as the reference's low byte, §3).
+DEV bool icmp_chunk_full(int32_t shift, uint32_t srcpad, uint32_t c, uint32_t chunks) {
+    const int32_t so = (int32_t)(16u * c) + shift;  // >= 4: c >= 2, shift >= -28
+    return c >= 2u && c < chunks && (uint32_t)so + 16u <= srcpad;  // inside the frame's chunks (live: below msg_base)
+}
+DEV uint4 icmp_chunk_load(const uint8_t* src, int32_t shift, uint32_t c, bool full) {
+    const uint8_t* p = full ? src + ((int32_t)(16u * c) + shift) : (const uint8_t*)g_zero_line;
+    const u32x4_a4_t x = __builtin_nontemporal_load((const u32x4_a4_t*)p);
+    return make_uint4(x.x, x.y, x.z, x.w);
+}
+DEV uint4 icmp_chunk_finish(const uint4& x, bool full, const uint8_t* src, int32_t shift, uint32_t c, uint32_t len, uint32_t h8,
+                            uint32_t h9, uint32_t h10, uint32_t& acc) {
+    const int32_t so = (int32_t)(16u * c) + shift;
+    uint32_t w[4] = {x.x, x.y, x.z, x.w};
+    if (!full) {
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t b = 16u * c + 4u * j;  // a dword the message needs starts inside the frame
+            w[j] = (b >= 44u && b < len) ? *(const uint32_t*)(src + so + (int32_t)(4u * j)) : 0u;
+        }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+        const uint32_t b = 16u * c + 4u * j;
+        const uint32_t keep = b >= len ? 0u : (len - b >= 4u ? 0xFFFFFFFFu : (1u << (8u * (len - b))) - 1u);
+        w[j] &= keep;
+    }
+    if (c == 2u) {  // bytes 32..43 are the plan's (already zero at and past len)
+        w[0] = h8;
+        w[1] = h9;
+        w[2] = h10;
+    }
+    acc = wsum(w[3], wsum(w[2], wsum(w[1], wsum(c == 2u ? w[0] & 0xFFFF0000u : w[0], acc))));
+    const uint32_t last = len - 1u;
+    const uint4 r = make_uint4(w[0], w[1], w[2], w[3]);
+    if ((len & 1u) && (last >> 4) == c) acc += 255u * ((comp(r, (last >> 2) & 3u) >> (8u * (last & 3u))) & 0xFFu);
+    return r;
+}
+
+__global__ __launch_bounds__(kIcmpTile) void icmp_emit_kernel(const IcmpView t, const FibView fib, const IcmpArgs a,
+                                                              uint32_t tiles, const FloodSum* __restrict__ sums) {
+    __shared__ FloodAcc wsum_lds[kFloodWaves];
+    __shared__ uint64_t m_at[kIcmpTile];
+    __shared__ uint32_t m_off16[kIcmpTile], m_srcpad[kIcmpTile], m_len[kIcmpTile], m_h8[kIcmpTile], m_h9[kIcmpTile],
+        m_h10[kIcmpTile];
+    __shared__ int32_t m_shift[kIcmpTile];
+    const uint32_t tile = xcd_block_n(tiles);
+    const uint64_t p = (uint64_t)tile * kIcmpTile + threadIdx.x;
+    uint2 d;
+    const IcmpPlan pl = icmp_classify(t, fib, a, p, &d);
+    const FloodAcc own = icmp_acc_of(pl, a.msg_align);
+    FloodAcc total;
+    const FloodAcc exc = flood_block_scan<kFloodWaves>(own, wsum_lds, &total);
+    const FloodAcc at = flood_add(flood_load(sums + tile), exc);  // what the packets before this one call for
+    // message k is emitted iff k < cap and msg_base + (slot bytes up to and including k) <= arena_bytes: the
+    // message before this packet's (region at.bytes) was emitted iff
+    const uint64_t region = flood_sat_add(a.msg_base, at.bytes);
+    const bool open = at.items <= a.cap && region <= a.arena_bytes;
+    const uint32_t e = (open && own.items && at.items < a.cap && a.arena_bytes - region >= own.bytes) ? 1u : 0u;
+    if (p < a.n) {
+        if (a.status) a.status[p] = (uint8_t)((own.items && !e) ? (uint32_t)NFCS_ICMP_ST_OVERFLOW : pl.status);
+        if (own.items) {  // exc.items < kIcmpTile: its place among the tile's messages
+            m_len[exc.items] = e ? pl.msg_len : 0u;
+            m_at[exc.items] = region;
+            m_off16[exc.items] = d.x;
+            m_srcpad[exc.items] = (d.y + 15u) & ~15u;  // wraps to 0 only above 2^32 - 16: dword loads then
+            m_shift[exc.items] = pl.shift;
+            m_h8[exc.items] = pl.hdr[8];
+            m_h9[exc.items] = pl.hdr[9];
+            m_h10[exc.items] = pl.hdr[10];
+        }
+        if (e) {  // at.items < cap; region + slot <= arena_bytes and the slot holds round_up(msg_len, 16)
+            ((uint2*)a.msg_desc)[at.items] = make_uint2((uint32_t)(region >> 4), pl.msg_len);
+            a.msg_port[at.items] = pl.port;
+            a.msg_src[at.items] = (uint32_t)p;
+            uint4* out = (uint4*)(a.arena + region);
+            vst16<NFCS_FLOOD_STORE>(out, make_uint4(pl.hdr[0], pl.hdr[1], pl.hdr[2], pl.hdr[3]));
+            vst16<NFCS_FLOOD_STORE>(out + 1, make_uint4(pl.hdr[4], pl.hdr[5], pl.hdr[6], pl.hdr[7]));
+        }
+        // the totals: from the packet that holds the cut, or from the last packet when nothing is cut
+        if (open && (e < own.items || p + 1u == a.n)) {
+            const FloodAcc all = flood_load(sums + tiles);
+            nfcs_icmp_totals r;
+            r.messages = at.items + e;
+            r.messages_needed = all.items;
+            r.echo_replies = at.copies + (e ? own.copies : 0u);
+            r.errors = r.messages - r.echo_replies;
+            r.msg_bytes = at.bytes + (e ? own.bytes : 0ull);
+            r.msg_bytes_needed = all.bytes;
+            *a.totals = r;
+        }
+    }
+    __syncthreads();
+    // the messages' chunks 2..: row `row` takes the tile's messages row, row + kIcmpRows, ...
+    const uint32_t nmsg = total.items, row = threadIdx.x / kIcmpR, rl = threadIdx.x % kIcmpR;
+    for (uint32_t f = row; f < nmsg; f += kIcmpRows) {
+        const uint32_t len = m_len[f];  // row-uniform; 0: not emitted. 42 <= len <= 65,549
+        if (len == 0u) continue;
+        const uint32_t chunks = (len + 15u) >> 4, srcpad = m_srcpad[f], h8 = m_h8[f], h9 = m_h9[f], h10 = m_h10[f];
+        const int32_t shift = m_shift[f];
+        const uint8_t* src = a.arena + (uint64_t)m_off16[f] * 16u;
+        uint4* out = (uint4*)(a.arena + m_at[f]);  // the slot ends inside the arena and holds `chunks` chunks
+        uint32_t acc = 0u;
+        uint4 v[kIcmpK];
+        bool full[kIcmpK];
+#pragma unroll
+        for (uint32_t s = 0; s < kIcmpK; ++s) {  // every load of the pass first
+            full[s] = icmp_chunk_full(shift, srcpad, rl + kIcmpR * s, chunks);
+            v[s] = icmp_chunk_load(src, shift, rl + kIcmpR * s, full[s]);
+        }
+#pragma unroll
+        for (uint32_t s = 0; s < kIcmpK; ++s) {
+            const uint32_t c = rl + kIcmpR * s;
+            if (c >= 2u && c < chunks) v[s] = icmp_chunk_finish(v[s], full[s], src, shift, c, len, h8, h9, h10, acc);
+        }
+        for (uint32_t c0 = kIcmpR * kIcmpK; c0 < chunks; c0 += kIcmpR * kIcmpK) {  // further passes: at most 42
+            uint4 w[kIcmpK];
+            bool wf[kIcmpK];
+#pragma unroll
+            for (uint32_t s = 0; s < kIcmpK; ++s) {
+                wf[s] = icmp_chunk_full(shift, srcpad, c0 + rl + kIcmpR * s, chunks);
+                w[s] = icmp_chunk_load(src, shift, c0 + rl + kIcmpR * s, wf[s]);
+            }
+#pragma unroll
+            for (uint32_t s = 0; s < kIcmpK; ++s) {
+                const uint32_t c = c0 + rl + kIcmpR * s;
+                if (c < chunks) vst16<NFCS_FLOOD_STORE>(out + c, icmp_chunk_finish(w[s], wf[s], src, shift, c, len, h8, h9, h10, acc));
+            }
+        }
+        const uint32_t csum = (~fold32(row_sum<16>(acc))) & 0xFFFFu;  // its two bytes in memory order, §3
+#pragma unroll
+        for (uint32_t s = 0; s < kIcmpK; ++s) {
+            const uint32_t c = rl + kIcmpR * s;
+            if (c == 2u) v[s].y |= csum;  // bytes 36-37 (zero in the plan)
+            if (c >= 2u && c < chunks) vst16<NFCS_FLOOD_STORE>(out + c, v[s]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void icmp_pad_kernel(const IcmpArgs a) {
+    const uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k >= a.cap || k < a.totals->messages) return;
+    ((uint2*)a.msg_desc)[k] = make_uint2(0u, 0u);
+    a.msg_port[k] = NFCS_IF_NONE;
+    a.msg_src[k] = NFCS_ITEM_NONE;
+}
+
+hipError_t launch_icmp_respond(const DevInfo& di, const IcmpView& icmp, const FibView& fib, const IcmpArgs& a,
+                               uint32_t* scratch, hipStream_t stream) {
+    (void)di;
+    if (a.n == 0) return hipSuccess;
+    const uint32_t tiles = (uint32_t)(((uint64_t)a.n + kIcmpTile - 1u) / kIcmpTile);
+    FloodSum* sums = (FloodSum*)scratch;  // tiles + 1 records (flood_scratch_words)
+    hipLaunchKernelGGL(icmp_count_kernel, dim3(tiles), dim3(kIcmpTile), 0, stream, icmp, fib, a, tiles, sums);
+    hipLaunchKernelGGL(flood_scan_kernel, dim3(1), dim3(kFloodScanThreads), 0, stream, sums, tiles);
+    hipLaunchKernelGGL(icmp_emit_kernel, dim3(tiles), dim3(kIcmpTile), 0, stream, icmp, fib, a, tiles, sums);
+    if (a.cap) {
+        const uint32_t g = (uint32_t)(((uint64_t)a.cap + kBlock - 1u) / kBlock);
+        hipLaunchKernelGGL(icmp_pad_kernel, dim3(g), dim3(kBlock), 0, stream, a);
     }
     return hipGetLastError();
 }
