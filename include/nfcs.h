@@ -148,6 +148,25 @@ NFCS_API int nfcs_ctx_set_slot_bytes(nfcs_ctx* ctx, uint32_t bytes);
  * No side effect; speed only (the bytes written never depend on it). */
 NFCS_API int nfcs_ctx_launch_footprint(nfcs_ctx* ctx, uint64_t arena_bytes, const nfcs_desc* d_desc,
                                        uint32_t n, uint64_t* mean);
+/* The form of nfcs_update_device on more than 65,536 long frames without d_patch:
+ * deferred (sub-batches of a read pass that writes patch records and a write pass that stores them: the
+ * fastest when most frames need their checksum bytes stored) or sparse (one read pass that stores the few
+ * differing fields inline: the fastest when hardly any frame does, as with received traffic). AUTO (the
+ * default) starts deferred and follows the store demand that the context's last calls observed: sparse
+ * once the two newest observations found nearly nothing to store, deferred again after one that did, and
+ * after a call on another stream than the previous update call's. Speed only: frame bytes, status bytes and
+ * records never depend on the form. A call with d_patch always runs deferred. These two symbols were added
+ * without changing NFCS_ABI_VERSION (it stays 2): detect them by symbol lookup. */
+#define NFCS_STORE_AUTO 0
+#define NFCS_STORE_DEFERRED 1
+#define NFCS_STORE_SPARSE 2
+NFCS_API int nfcs_ctx_set_store_policy(nfcs_ctx* ctx, int policy);
+/* *form = the form the newest nfcs_update_device call on ctx ran in (NFCS_STORE_DEFERRED or
+ * NFCS_STORE_SPARSE; 0: none yet, or a call the forms do not apply to); *sampled / *storing = the newest
+ * store-demand observation a finished call has delivered: how many packets it sampled and how many of
+ * them needed a store (both 0: none yet). A call's observation is delivered by the next such call on the
+ * context once that has started. Any pointer may be null. For tests and tools. */
+NFCS_API int nfcs_ctx_store_state(nfcs_ctx* ctx, int* form, uint32_t* sampled, uint32_t* storing);
 /* The host staging ring of nfcs_update_host (allocated by this call if not yet): *node = the GPU's
  * NUMA node (-1 if unknown), *local = 1 when the ring's pinned memory is bound to that node (its
  * copy threads then run on that node's CPUs). SURVEY.md §8e: one GPU per host thread, staging
@@ -1281,6 +1300,14 @@ NFCS_API int nfcs_layout_config(int config, uint64_t seed, uint64_t first_index,
 NFCS_API int nfcs_gen_config_device(nfcs_ctx* ctx, int config, uint64_t seed,
                                     uint64_t first_index, uint32_t n, uint8_t* d_arena,
                                     uint64_t arena_bytes, const nfcs_desc* d_desc, void* stream);
+
+/* A measurement helper: flips the high byte of the IPv4 (byte 24) and the L4 (byte 40) checksum field of
+ * one frame (at a hashed place) in every group of `every` consecutive frames (0: none) of a batch of untagged UDP-over-IPv4 frames such as config C1's, so that
+ * the next update finds exactly those frames in need of a store (tools/store_case_bench.py --stale-every).
+ * Frames shorter than 42 bytes or outside the arena are left alone. Added without changing
+ * NFCS_ABI_VERSION. */
+NFCS_API int nfcs_stale_every_device(nfcs_ctx* ctx, uint8_t* d_arena, uint64_t arena_bytes,
+                                     const nfcs_desc* d_desc, uint32_t n, uint32_t every, void* stream);
 
 /* Order-independent 64-bit digest of the n frames (packet index first_index + i):
  *   digest = sum_i mix64(frame_hash(frame_i) ^ ((first_index + i) * 0xA0761D6478BD642F))

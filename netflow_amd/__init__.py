@@ -116,6 +116,8 @@ assert FLOW_KEY_DTYPE.itemsize == 64
 CFG_C0, CFG_C1, CFG_C2, CFG_C3 = 0, 1, 2, 3
 HOST_PATCH_ONLY, HOST_ZERO_COPY, HOST_FRAMES = 1, 2, 4
 PATCH_NONE = 0xFFFF
+# nfcs_ctx_set_store_policy / nfcs_ctx_store_state (include/nfcs.h NFCS_STORE_*)
+STORE_AUTO, STORE_DEFERRED, STORE_SPARSE = 0, 1, 2
 
 
 class NfcsError(RuntimeError):
@@ -160,6 +162,9 @@ def _declare(L):
         "nfcs_ctx_stream": ([_vp], _vp),
         "nfcs_ctx_set_slot_bytes": ([_vp, ctypes.c_uint32], ctypes.c_int),
         "nfcs_ctx_launch_footprint": ([_vp, _u64, _vp, _u32, ctypes.POINTER(_u64)], ctypes.c_int),
+        "nfcs_ctx_set_store_policy": ([_vp, ctypes.c_int], ctypes.c_int),
+        "nfcs_ctx_store_state": ([_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(_u32), ctypes.POINTER(_u32)],
+                                 ctypes.c_int),
         "nfcs_update_device": ([_vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp], ctypes.c_int),
         "nfcs_update_host": ([_vp, _vp, _u64, _vp, _u32, _vp, _u32], ctypes.c_int),
         "nfcs_update_host_frames": ([_vp, _vp, _vp, _u32, _vp, _u32], ctypes.c_int),
@@ -167,6 +172,7 @@ def _declare(L):
         "nfcs_shard_bytes": ([_vp, _u32, _u32, _vp], ctypes.c_int),
         "nfcs_ctx_host_numa": ([_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
         "nfcs_gen_config_device": ([_vp, ctypes.c_int, _u64, _u64, _u32, _vp, _u64, _vp, _vp], ctypes.c_int),
+        "nfcs_stale_every_device": ([_vp, _vp, _u64, _vp, _u32, _u32, _vp], ctypes.c_int),
         "nfcs_digest_device": ([_vp, _vp, _u64, _vp, _u32, _u64, ctypes.POINTER(_u64), _vp], ctypes.c_int),
         "nfcs_device_alloc": ([_vp, ctypes.c_size_t, ctypes.POINTER(_vp)], ctypes.c_int),
         "nfcs_device_free": ([_vp, _vp], ctypes.c_int),
@@ -1058,6 +1064,19 @@ class Engine:
         _check(lib().nfcs_ctx_launch_footprint(self.ctx, arena_bytes, p, n, ctypes.byref(m)), "launch_footprint")
         return int(m.value)
 
+    def set_store_policy(self, policy: int):
+        """The form of large long-frame device updates (nfcs_ctx_set_store_policy): STORE_AUTO (the default:
+        by the store demand of the last calls), STORE_DEFERRED or STORE_SPARSE. Speed only."""
+        _check(lib().nfcs_ctx_set_store_policy(self.ctx, int(policy)), "set_store_policy")
+
+    def store_state(self) -> tuple[int, int, int]:
+        """(form the newest device update ran in: STORE_DEFERRED, STORE_SPARSE or 0; packets sampled; packets of
+        them that needed a store) of the newest delivered observation (nfcs_ctx_store_state)."""
+        form, sampled, storing = ctypes.c_int(), _u32(), _u32()
+        _check(lib().nfcs_ctx_store_state(self.ctx, ctypes.byref(form), ctypes.byref(sampled), ctypes.byref(storing)),
+               "store_state")
+        return form.value, int(sampled.value), int(storing.value)
+
     def host_numa(self) -> tuple[int, bool]:
         """(NUMA node of this GPU or -1, whether the host staging ring is bound to it)."""
         node, local = ctypes.c_int(), ctypes.c_int()
@@ -1344,6 +1363,13 @@ class Engine:
                           arena: DeviceBuffer, arena_bytes: int, desc: DeviceBuffer, stream=None):
         _check(lib().nfcs_gen_config_device(self.ctx, config, seed, first, n, arena.ptr, arena_bytes,
                                             desc.ptr, stream), "gen_config_device")
+
+    def stale_every_device(self, arena: DeviceBuffer, arena_bytes: int, desc: DeviceBuffer, n: int, every: int,
+                           stream=None):
+        """Make the checksum fields of every `every`-th frame of an updated C1-shaped batch stale again
+        (nfcs_stale_every_device; a measurement helper)."""
+        _check(lib().nfcs_stale_every_device(self.ctx, arena.ptr, arena_bytes, desc.ptr, n, every, stream),
+               "stale_every_device")
 
     def digest_device(self, arena: DeviceBuffer, arena_bytes: int, desc: DeviceBuffer, n: int,
                       first: int = 0, stream=None) -> int:

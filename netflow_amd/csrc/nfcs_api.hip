@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "nfcs_internal.h"
+#include "nfcs_store_policy.h"
 
 // Pinned host memory for the staging ring, on the GPU's NUMA node when that is known: mmap'd,
 // bound to the node (mbind, MPOL_PREFERRED), faulted in there, then registered with HIP; else
@@ -186,6 +187,23 @@ struct nfcs_ctx {
     ObsBurst obs_burst[kObsSlots] = {};
     uint32_t obs_gen = 0;   // the last generation handed out (0: never; slots start empty)
     uint64_t obs_clock = 0;
+    // Store demand (nfcs_internal.h DemandReq, nfcs_store_policy.h): two buffers of counter words in
+    // device memory, alternating by the call's generation; the host-mapped word the next call forwards a
+    // call's count to; how many packets each of the last calls sampled (the host knows it from n alone);
+    // and the policy over the observations read so far. dem_last_form: the form the newest update call
+    // ran in (NFCS_STORE_DEFERRED / NFCS_STORE_SPARSE; 0: none yet, or a call the forms do not apply to).
+    static constexpr int kDemRing = 64;  // calls the host may be ahead of the device and still place an observation
+    uint32_t* dem_dev = nullptr;
+    uint64_t* dem_host = nullptr;
+    uint64_t* dem_host_dev = nullptr;
+    uint32_t dem_gen = 0;
+    struct DemCall { uint32_t gen, sampled; };
+    DemCall dem_calls[kDemRing] = {};
+    nfcs::StorePolicy dem_policy;
+    int store_policy = NFCS_STORE_AUTO;
+    int dem_last_form = 0;
+    hipStream_t dem_stream = nullptr;
+    bool dem_any = false;  // dem_stream is the stream of the previous update call
 };
 
 namespace {
@@ -836,12 +854,55 @@ Shape launch_shape(nfcs_ctx* c, uint64_t arena_bytes, const nfcs_desc* d_desc, u
 
 // The device-resident update on stream st: kUpdateAuto, deferred records into the caller's
 // d_patch when given, else into the context workspace.
+// The newest store-demand observation the device has forwarded, fed to the policy (no sync: a word the
+// device writes with one 64-bit store; a generation the context no longer remembers is skipped).
+void read_store_demand(nfcs_ctx* c) {
+    if (!c->dem_host) return;
+    const uint64_t o = __atomic_load_n(c->dem_host, __ATOMIC_RELAXED);
+    const uint32_t gen = (uint32_t)(o >> 32);
+    if (!c->dem_policy.newer(gen)) return;
+    const nfcs_ctx::DemCall& dc = c->dem_calls[gen % nfcs_ctx::kDemRing];
+    if (dc.gen == gen) c->dem_policy.observe(gen, dc.sampled, (uint32_t)o);
+}
+
+// A long-shape call of more than kInlineMaxPackets packets runs deferred (sub-batches of a read pass
+// writing records and a write pass) or sparse (one inline launch), by the context's policy over the store
+// demand of its last calls (nfcs_store_policy.h). Speed only: bytes, status bytes and
+// records never depend on the form. A caller's d_patch keeps the call deferred (its records hold every
+// field); a call on another stream than the previous update call's returns the context to deferred, since
+// calls that may run concurrently share the counters.
 int update_device(nfcs_ctx* c, uint8_t* d_arena, uint64_t arena_bytes, const nfcs_desc* d_desc,
                   uint32_t n, uint8_t* d_status, nfcs_patch* d_patch, hipStream_t st) {
     if (!d_patch) NFCS_HIP(acquire_ws(c, n, st));
     const Shape sh = launch_shape(c, arena_bytes, d_desc, n);
+    nfcs::DemandReq dem;
+    bool sparse = false;
+    const bool changed = c->dem_any && c->dem_stream != st;
+    c->dem_stream = st;
+    c->dem_any = true;
+    c->dem_last_form = 0;
+    // the next two counting calls use buffers that a call still running on the other stream may be
+    // forwarding or counting into: their observations are skipped
+    if (changed) c->dem_policy.reset(c->dem_gen + 2u);
+    if (c->dem_dev && nfcs::update_demand_sampled(arena_bytes, n, sh.mean, false)) {
+        read_store_demand(c);
+        if (!d_patch)
+            sparse = c->store_policy == NFCS_STORE_SPARSE ||
+                     (c->store_policy == NFCS_STORE_AUTO && c->dem_policy.form == nfcs::kStoreFormSparse);
+        const uint32_t prev = c->dem_gen;
+        if (++c->dem_gen == 0) c->dem_gen = 1;
+        const uint32_t words = nfcs::kDemandWords * nfcs::kDemandStrideWords;
+        c->dem_calls[c->dem_gen % nfcs_ctx::kDemRing] = {c->dem_gen,
+                                                         nfcs::update_demand_sampled(arena_bytes, n, sh.mean, sparse)};
+        dem.cur = c->dem_dev + (c->dem_gen & 1u) * words;
+        dem.prev = c->dem_dev + (prev & 1u) * words;
+        dem.host = prev ? c->dem_host_dev : nullptr;
+        dem.prev_gen = prev;
+        if (prev && (prev & 1u) == (c->dem_gen & 1u)) dem.host = nullptr;  // the generation wrapped past 0
+        c->dem_last_form = sparse ? NFCS_STORE_SPARSE : NFCS_STORE_DEFERRED;
+    }
     NFCS_HIP(nfcs::launch_update(c->di, d_arena, arena_bytes, d_desc, n, 0u, d_status, d_patch,
-                                 d_patch ? nullptr : c->ws, nfcs::kUpdateAuto, st, sh.mean, sh.obs));
+                                 d_patch ? nullptr : c->ws, nfcs::kUpdateAuto, st, sh.mean, sh.obs, {}, dem, sparse));
     if (!d_patch) NFCS_HIP(release_ws(c, st));
     return NFCS_OK;
 }
@@ -908,6 +969,14 @@ NFCS_API int nfcs_ctx_create(int device, nfcs_ctx** out) {
         for (int k = 0; k < nfcs_ctx::kObsSlots; ++k) c->obs_host[k] = 0;
         e = hipHostGetDevicePointer((void**)&c->obs_dev, c->obs_host, 0);
     }
+    const size_t dem_bytes = 2u * nfcs::kDemandWords * nfcs::kDemandStrideWords * sizeof(uint32_t);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->dem_dev, dem_bytes);
+    if (e == hipSuccess) e = hipMemset(c->dem_dev, 0, dem_bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&c->dem_host, sizeof(uint64_t), hipHostMallocMapped);
+    if (e == hipSuccess) {
+        *c->dem_host = 0;
+        e = hipHostGetDevicePointer((void**)&c->dem_host_dev, c->dem_host, 0);
+    }
     if (e != hipSuccess) {
         nfcs_ctx_destroy(c);
         return hip_fail(e);
@@ -932,6 +1001,8 @@ NFCS_API int nfcs_ctx_destroy(nfcs_ctx* c) {
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->obs_host) (void)hipHostFree(c->obs_host);
+    if (c->dem_host) (void)hipHostFree(c->dem_host);
+    if (c->dem_dev) (void)hipFree(c->dem_dev);
     delete c;
     return NFCS_OK;
 }
@@ -941,6 +1012,22 @@ NFCS_API void* nfcs_ctx_stream(nfcs_ctx* c) { return c ? (void*)c->stream : null
 NFCS_API int nfcs_ctx_set_slot_bytes(nfcs_ctx* c, uint32_t bytes) {
     if (!c) return NFCS_EINVAL;
     c->slot_bytes = bytes;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_ctx_set_store_policy(nfcs_ctx* c, int policy) {
+    if (!c || (policy != NFCS_STORE_AUTO && policy != NFCS_STORE_DEFERRED && policy != NFCS_STORE_SPARSE))
+        return NFCS_EINVAL;
+    c->store_policy = policy;
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_ctx_store_state(nfcs_ctx* c, int* form, uint32_t* sampled, uint32_t* storing) {
+    if (!c) return NFCS_EINVAL;
+    read_store_demand(c);
+    if (form) *form = c->dem_last_form;
+    if (sampled) *sampled = c->dem_policy.obs_sampled;
+    if (storing) *storing = c->dem_policy.obs_storing;
     return NFCS_OK;
 }
 
@@ -2679,6 +2766,17 @@ NFCS_API int nfcs_gen_config_device(nfcs_ctx* c, int config, uint64_t seed, uint
     NFCS_HIP(hipMemsetAsync(d_arena, 0, arena_bytes, pick(c, stream)));
     NFCS_HIP(nfcs::launch_gen_config(c->di, config, seed, first, n, d_arena, arena_bytes, d_desc,
                                      pick(c, stream)));
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_stale_every_device(nfcs_ctx* c, uint8_t* d_arena, uint64_t arena_bytes,
+                                     const nfcs_desc* d_desc, uint32_t n, uint32_t every, void* stream) {
+    if (!c) return NFCS_EINVAL;
+    DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    if (n == 0 || every == 0) return NFCS_OK;
+    if (!d_arena || !d_desc) return NFCS_EINVAL;
+    NFCS_HIP(nfcs::launch_stale_every(d_arena, arena_bytes, d_desc, n, every, pick(c, stream)));
     return NFCS_OK;
 }
 

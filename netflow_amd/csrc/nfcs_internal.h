@@ -170,10 +170,40 @@ struct DoneReq {
     uint64_t base = 0;
 };
 
+// A store-demand request (the plain update's long shape; for the next calls' form, nfcs_store_policy.h):
+// one workgroup in kDemandSampleEvery (by its place in the batch) counts the packets whose frame still
+// needs a store (a checksum field that differs, or an uncommon header) into `cur`, kDemandWords words
+// kDemandStrideWords apart (a line each) in device memory, consecutive sampled workgroups on consecutive
+// words; a wave with none issues nothing. (One workgroup in 16 on one word per XCD cost the
+// every-packet-stores case 7%: 16K atomics per 1M-packet call queued on 8 addresses) The first wave
+// of a call with `host` set also forwards the PREVIOUS call's total from `prev` to *host (host-mapped)
+// as prev_gen << 32 | total, and clears `prev` for the next call: the context alternates two buffers, and
+// calls on one stream run in order, so no barrier, extra launch or copy is needed. cur null: none.
+struct DemandReq {
+    uint32_t* cur = nullptr;
+    uint32_t* prev = nullptr;
+    uint64_t* host = nullptr;
+    uint32_t prev_gen = 0;
+};
+constexpr uint32_t kDemandSampleEvery = 64;  // a power of two
+constexpr uint32_t kDemandWords = 64, kDemandStrideWords = 32;  // one word per lane of the forwarding wave
+constexpr uint32_t kDemandBlockPackets = 16;  // packets per workgroup of the long shape
+// The packets one launch over n packets samples: those of workgroups 0, 64, 128, ... of the batch.
+inline uint32_t demand_sampled_one(uint32_t n) {
+    const uint32_t span = kDemandSampleEvery * kDemandBlockPackets;
+    const uint32_t rest = n % span;
+    return n / span * kDemandBlockPackets + (rest < kDemandBlockPackets ? rest : kDemandBlockPackets);
+}
+
+// form kUpdateAuto, sparse: a long-shape call of any size runs as one inline launch (no sub-batches, no
+// records, no write pass), as bursts of at most kInlineMaxPackets do; other shapes are unaffected.
 hipError_t launch_update(const DevInfo& di, uint8_t* arena, uint64_t arena_bytes,
                          const nfcs_desc* desc, uint32_t n, uint32_t base16, uint8_t* status,
                          nfcs_patch* patch, nfcs_patch* ws, int form, hipStream_t stream,
-                         uint64_t slot_bytes = 0, ObsReq obs = {}, DoneReq done = {});
+                         uint64_t slot_bytes = 0, ObsReq obs = {}, DoneReq done = {}, DemandReq dem = {},
+                         bool sparse = false);
+// The packets that call samples for its DemandReq (0: it runs no long-shape read pass that counts).
+uint32_t update_demand_sampled(uint64_t arena_bytes, uint32_t n, uint64_t slot_bytes, bool sparse);
 
 hipError_t launch_l3_forward(const DevInfo& di, uint8_t* arena, uint64_t arena_bytes,
                              const nfcs_desc* desc, const uint32_t* nh, uint32_t n,
@@ -347,6 +377,8 @@ struct IcmpArgs {
 hipError_t launch_icmp_respond(const DevInfo& di, const IcmpView& icmp, const FibView& fib, const IcmpArgs& a,
                                uint32_t* scratch, hipStream_t stream);
 
+hipError_t launch_stale_every(uint8_t* arena, uint64_t arena_bytes, const nfcs_desc* desc, uint32_t n,
+                              uint32_t every, hipStream_t stream);
 hipError_t launch_gen_config(const DevInfo& di, int config, uint64_t seed, uint64_t first,
                              uint32_t n, uint8_t* arena, uint64_t arena_bytes,
                              const nfcs_desc* desc, hipStream_t stream);

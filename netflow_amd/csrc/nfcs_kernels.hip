@@ -700,6 +700,7 @@ struct FwdArgs {
     uint32_t table_n;
     ObsReq obs;
     DoneReq done = {};
+    DemandReq dem = {};
 };
 
 // DoneReq (nfcs_internal.h): every wave releases its own frame / record / status stores at system scope
@@ -764,6 +765,22 @@ DEV void sample_footprint(const nfcs_desc* __restrict__ desc, uint64_t tag, uint
     if (lane == 0)
         __hip_atomic_store(obs, (tag & 0xFFFFFFFF00000000ull) | kObsPresent | bits | (l << kObsLongShift) | (t >> 8),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// The previous call's store demand, forwarded by one wave of this call (DemandReq): each lane reads and
+// clears one of the 64 words (that call has finished: calls on one stream run in order), and lane 0
+// writes their total with that call's generation to the host-mapped word in one 64-bit store, as
+// sample_footprint does. Speed only (the next calls' form, nfcs_store_policy.h).
+DEV void forward_demand(const DemandReq& d, uint32_t lane) {
+    static_assert(kDemandWords == 64, "one word per lane");
+    uint32_t* w = d.prev + lane * kDemandStrideWords;
+    uint32_t v = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    v = row_sum<16>(v);
+    v = (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
+        (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+    if (lane == 0)
+        __hip_atomic_store(d.host, ((uint64_t)d.prev_gen << 32) | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // Issue the row's K chunk loads: the header slot with the default cache policy (its lines are
@@ -881,7 +898,8 @@ DEV uint4 hdr_view(const RowStage<K>& S, uint32_t rowbase4, uint32_t rl) {
 template <int K, int R = 16, bool FWD = false, bool NT = false, bool DFR = false, bool LA = false>
 DEV void row_process(const RowStage<K>& S, uint32_t rl, uint32_t rowbase4, uint8_t* status,
                      nfcs_patch* rec, bool rec_full, bool frame_stores, uint32_t table_n = 0,
-                     const uint32_t* wmac = nullptr, const nfcs_nexthop* table = nullptr) {
+                     const uint32_t* wmac = nullptr, const nfcs_nexthop* table = nullptr,
+                     uint32_t* demand = nullptr) {
     const uint32_t len = S.len;
     uint8_t* frame = S.frame;
     const uint4* src = (const uint4*)frame;
@@ -1080,6 +1098,15 @@ DEV void row_process(const RowStage<K>& S, uint32_t rl, uint32_t rowbase4, uint8
             ((uint2*)rec)[S.p] = (fwd && live) ? fwd_record(ipw, l4w, ttl - 1u, proto, tagged) : make_uint2(0xFFFFFFFFu, 0u);
     } else {
         emit(S.valid && !slow, st, ipw, l4w, sipw, sl4w, frame_stores);
+        // Store demand (DemandReq; a sampled workgroup of the long shape, wave-uniform): the wave's
+        // packets whose frame still needs a store, one ballot and one count, and one returnless atomic
+        // from one lane only when there are any: a wave of frames that are already right issues nothing.
+        if (demand) {
+            const bool need = slow || (sipw & 0xFFFFu) != NFCS_PATCH_NONE || (sl4w & 0xFFFFu) != NFCS_PATCH_NONE;
+            const uint32_t cnt = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(need && rl == 0));
+            if (cnt != 0 && rl == 0 && rowbase4 == 0)
+                (void)__hip_atomic_fetch_add(demand, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
     if (__builtin_amdgcn_ballot_w64(slow) != 0) {  // cold path, wave-uniform branch
         // Uncommon headers, handled last so that only the frame address and length are live
@@ -1171,7 +1198,8 @@ DEV void row_process(const RowStage<K>& S, uint32_t rl, uint32_t rowbase4, uint8
 template <int K, int R, int BS, bool FWD, int SF, bool LA, int PW>
 DEV void rows_body(const DescW<PW>& D, uint64_t pw, uint32_t n, uint8_t* arena, uint64_t arena_bytes, uint32_t base16,
                    uint32_t rl, uint32_t row, uint32_t rowbase4, bool defer, const uint32_t (&q)[PW],
-                   uint8_t* status, nfcs_patch* patch, nfcs_patch* ws, const nfcs_nexthop* table, uint32_t table_n) {
+                   uint8_t* status, nfcs_patch* patch, nfcs_patch* ws, const nfcs_nexthop* table, uint32_t table_n,
+                   uint32_t* demand) {
     typedef const __attribute__((address_space(4))) uint32_t cu32;
     const bool frame_stores = SF == SF_INLINE || (SF == SF_DEFER && !defer);
     nfcs_patch* rec = patch ? patch : (defer ? ws : nullptr);
@@ -1205,7 +1233,7 @@ DEV void rows_body(const DescW<PW>& D, uint64_t pw, uint32_t n, uint8_t* arena, 
     // windows), write-through elsewhere (see row_process)
     row_process<K, R, FWD, !FWD && R == 16 && !LA, FWD && SF == SF_DEFER, LA>(S, rl, rowbase4, status, rec,
                                                                                  patch != nullptr, frame_stores, table_n,
-                                                                                 wmac, table);
+                                                                                 wmac, table, demand);
 }
 
 // One wave of update_rows_kernel: its PW packets from the descriptor load on.
@@ -1214,7 +1242,7 @@ DEV void rows_wave(const nfcs_desc* __restrict__ desc, uint32_t n, uint8_t* __re
                    uint32_t base16, const uint32_t* __restrict__ nh, uint64_t* __restrict__ obs,
                    uint8_t* __restrict__ status, nfcs_patch* __restrict__ patch, nfcs_patch* __restrict__ ws,
                    const nfcs_nexthop* __restrict__ table, uint32_t table_n, uint64_t obs_tag, uint32_t lane,
-                   uint32_t rl, uint32_t row, uint32_t rowbase4, uint64_t pw) {
+                   uint32_t rl, uint32_t row, uint32_t rowbase4, uint64_t pw, uint32_t* demand) {
     constexpr uint32_t PW = 64 / R;  // packets per wave
     if (blockIdx.x == 0 && threadIdx.x < 64 && obs) sample_footprint(desc, obs_tag, lane, obs);
     // the wave's PW descriptors: one scalar load (s_load_dwordx8 for PW = 4)
@@ -1258,10 +1286,10 @@ DEV void rows_wave(const nfcs_desc* __restrict__ desc, uint32_t n, uint8_t* __re
     }
     if (la)
         rows_body<KL, R, BS, FWD, SF, true, PW>(D, pw, n, arena, arena_bytes, base16, rl, row, rowbase4, defer, q,
-                                                status, patch, ws, table, table_n);
+                                                status, patch, ws, table, table_n, demand);
     else
         rows_body<K, R, BS, FWD, SF, false, PW>(D, pw, n, arena, arena_bytes, base16, rl, row, rowbase4, defer, q,
-                                                status, patch, ws, table, table_n);
+                                                status, patch, ws, table, table_n, demand);
 }
 
 // LAM: 0 frame-relative windows of K slots; 1 line-aligned windows of KL slots; 2 per wave, line-
@@ -1277,16 +1305,27 @@ __global__ __launch_bounds__(BS, OCC) void update_rows_kernel(const nfcs_desc* _
                                                               nfcs_patch* __restrict__ patch,
                                                               nfcs_patch* __restrict__ ws,
                                                               const nfcs_nexthop* __restrict__ table,
-                                                              uint32_t table_n, uint64_t obs_tag, DoneReq done) {
+                                                              uint32_t table_n, uint64_t obs_tag, DoneReq done,
+                                                              DemandReq dem) {
     constexpr uint32_t PW = 64 / R;  // packets per wave
     const uint32_t lane = threadIdx.x & 63u, rl = lane & (R - 1), row = lane / R;
     const uint32_t rowbase4 = (lane & ~(uint32_t)(R - 1)) * 4u;
-    const uint64_t pw = (uint64_t)xcd_block_n(nblocks) * (BS / R) + rfl(threadIdx.x >> 6) * PW;
+    const uint32_t lb = xcd_block_n(nblocks);
+    const uint64_t pw = (uint64_t)lb * (BS / R) + rfl(threadIdx.x >> 6) * PW;
     // with a DoneReq (a kernel argument: uniform) waves without packets stay for signal_done's barrier
     if (pw >= n && !done.flag) return;
+    // Store demand: the plain update's long shape only (its workgroups hold kDemandBlockPackets packets)
+    constexpr bool DEM = !FWD && R == 16 && LAM == 1 && BS == kBlock && SF != SF_RECORDS;
+    uint32_t* demand = nullptr;
+    if (DEM && dem.cur) {
+        static_assert(!DEM || BS / R == (int)kDemandBlockPackets, "demand_sampled_one counts 16-packet workgroups");
+        if ((lb & (kDemandSampleEvery - 1u)) == 0)
+            demand = dem.cur + ((lb / kDemandSampleEvery) & (kDemandWords - 1u)) * kDemandStrideWords;
+        if (blockIdx.x == 0 && threadIdx.x < 64 && dem.host) forward_demand(dem, lane);
+    }
     if (pw < n)
         rows_wave<K, R, BS, FWD, SF, LAM, KL>(desc, n, arena, arena_bytes, base16, nh, obs, status, patch, ws, table,
-                                              table_n, obs_tag, lane, rl, row, rowbase4, pw);
+                                              table_n, obs_tag, lane, rl, row, rowbase4, pw, demand);
     if (done.flag) signal_done(done, nblocks);
 }
 
@@ -1437,15 +1476,16 @@ static void launch_rows(uint32_t grid, unsigned lds, hipStream_t stream, uint8_t
                         nfcs_patch* ws, const FwdArgs& fa) {
     hipLaunchKernelGGL((update_rows_kernel<K, R, OCC, BS, FWD, SF, LAM, KL>), dim3(grid), dim3(BS), lds, stream, desc, n, grid,
                        arena, arena_bytes, base16, fa.nh, fa.obs.slot, status, patch, ws, fa.table, fa.table_n,
-                       fa.obs.tag, fa.done);
+                       fa.obs.tag, fa.done, fa.dem);
 }
 
 // One launch of the checksum path (its read pass and, for kUpdateAuto, its write pass) over n
 // packets, in the shape chosen for the whole call.
 static hipError_t launch_update_one(uint8_t* arena, uint64_t arena_bytes, const nfcs_desc* desc, uint32_t n,
                                     uint32_t base16, uint8_t* status, nfcs_patch* patch, nfcs_patch* ws,
-                                    int form, int shape, hipStream_t stream, ObsReq obs, DoneReq done = {}) {
-    const FwdArgs nofwd = {nullptr, nullptr, 0, obs, done};
+                                    int form, int shape, hipStream_t stream, ObsReq obs, DoneReq done = {},
+                                    DemandReq dem = {}) {
+    const FwdArgs nofwd = {nullptr, nullptr, 0, obs, done, dem};
     // a burst of at most kInlineMaxPackets packets: one kernel, every wave inline (the write pass's
     // launch would cost more than deferral saves on so few packets)
     if (form == kUpdateAuto && n <= kInlineMaxPackets) form = kUpdateInline;
@@ -1490,7 +1530,7 @@ static hipError_t launch_update_one(uint8_t* arena, uint64_t arena_bytes, const 
 hipError_t launch_update(const DevInfo& di, uint8_t* arena, uint64_t arena_bytes,
                          const nfcs_desc* desc, uint32_t n, uint32_t base16, uint8_t* status,
                          nfcs_patch* patch, nfcs_patch* ws, int form, hipStream_t stream,
-                         uint64_t slot_bytes, ObsReq obs, DoneReq done) {
+                         uint64_t slot_bytes, ObsReq obs, DoneReq done, DemandReq dem, bool sparse) {
     (void)di;
     if (n == 0) return hipSuccess;
     if (form == kUpdateRecords && !patch) return hipErrorInvalidValue;
@@ -1514,17 +1554,35 @@ hipError_t launch_update(const DevInfo& di, uint8_t* arena, uint64_t arena_bytes
     // shard 0.683-0.714 -> 0.749-0.755). Sub-batches are multiples of 4 packets, so every wave's
     // deferral group is the same as in one launch; they run in order on the stream and share the
     // workspace.
+    // The sparse form (nfcs_store_policy.h: the context's recent calls found next to nothing to store): the
+    // whole call as one inline launch, as a burst of at most kInlineMaxPackets runs; never with a caller's
+    // records, which keep every field.
+    // One launch whatever the size: as 512K sub-batches the sparse form measured 1-2% slower on C1 and 3-4%
+    // on the 4M shard (profiles/store_policy_sub_batches.jsonl).
+    if (form == kUpdateAuto && shape == kShapeLong && sparse && !patch) form = kUpdateInline;
     if (form == kUpdateAuto && shape == kShapeLong && n > kSubBatchAbovePackets) {
         for (uint32_t i = 0; i < n; i += kSubBatchPackets) {
+            // every sub-batch counts its store demand into the call's words; the first forwards the
+            // previous call's
+            const DemandReq ds = {dem.cur, dem.prev, i == 0 ? dem.host : nullptr, dem.prev_gen};
             const hipError_t e = launch_update_one(arena, arena_bytes, desc + i, std::min(kSubBatchPackets, n - i),
                                                    base16, status ? status + i : nullptr,
                                                    patch ? patch + i : nullptr, ws, form, shape, stream,
-                                                   i == 0 ? obs : ObsReq{});
+                                                   i == 0 ? obs : ObsReq{}, DoneReq{}, ds);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
     }
-    return launch_update_one(arena, arena_bytes, desc, n, base16, status, patch, ws, form, shape, stream, obs, done);
+    return launch_update_one(arena, arena_bytes, desc, n, base16, status, patch, ws, form, shape, stream, obs, done,
+                             dem);
+}
+
+uint32_t update_demand_sampled(uint64_t arena_bytes, uint32_t n, uint64_t slot_bytes, bool sparse) {
+    if (n <= kInlineMaxPackets || shape_mean(arena_bytes, n, slot_bytes) < kSmallMeanBytes) return 0;
+    if (sparse || n <= kSubBatchAbovePackets) return demand_sampled_one(n);
+    uint32_t s = 0;
+    for (uint32_t i = 0; i < n; i += kSubBatchPackets) s += demand_sampled_one(std::min(kSubBatchPackets, n - i));
+    return s;
 }
 
 hipError_t launch_l3_forward(const DevInfo& di, uint8_t* arena, uint64_t arena_bytes,
@@ -3749,6 +3807,39 @@ hipError_t launch_gen_config(const DevInfo& di, int config, uint64_t seed, uint6
     if (grid > (uint32_t)di.cus * 8u) grid = (uint32_t)di.cus * 8u;
     hipLaunchKernelGGL(gen_config_kernel, dim3(grid), dim3(kBlock), 0, stream, config, seed,
                        first, n, arena, arena_bytes, desc);
+    return hipGetLastError();
+}
+
+// A measurement helper (tools/store_case_bench.py --stale-every): one thread per group of `every`
+// consecutive packets of an updated batch of untagged IPv4 frames with the L4 checksum at byte 40 (C1's
+// UDP) flips the high byte of both checksum fields of one packet of the group, so the next update finds
+// exactly those packets in need of a store. The packet's place in its group is hashed: with a fixed place
+// the stale frames of a uniform batch lie at one stride (every 256th C1 frame: 384 KB), their partial
+// writes fall on a few memory channels, and the sweep measured that aliasing instead of the store form
+// (DESIGN.md §12). Untimed.
+__global__ __launch_bounds__(kBlock) void stale_every_kernel(uint8_t* __restrict__ arena, uint64_t arena_bytes,
+                                                             const nfcs_desc* __restrict__ desc, uint32_t n,
+                                                             uint32_t every) {
+    const uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    uint32_t h = (uint32_t)g * 0x9E3779B1u;
+    h ^= h >> 15;
+    h *= 0x85EBCA77u;
+    h ^= h >> 13;
+    const uint64_t p = g * every + h % every;
+    if (p >= n) return;
+    const nfcs_desc d = desc[p];
+    const uint64_t off = (uint64_t)d.off16 * 16u;
+    if (d.len < 42u || off + (((uint64_t)d.len + 15u) & ~15ull) > arena_bytes) return;
+    arena[off + 24u] ^= 0xFFu;
+    arena[off + 40u] ^= 0xFFu;
+}
+
+hipError_t launch_stale_every(uint8_t* arena, uint64_t arena_bytes, const nfcs_desc* desc, uint32_t n,
+                              uint32_t every, hipStream_t stream) {
+    if (n == 0 || every == 0) return hipSuccess;
+    const uint32_t m = (n + every - 1u) / every;
+    hipLaunchKernelGGL(stale_every_kernel, dim3((m + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, arena,
+                       arena_bytes, desc, n, every);
     return hipGetLastError();
 }
 

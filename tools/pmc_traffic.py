@@ -41,17 +41,20 @@ def threads_per_packet(kernel_name: str) -> int:
     return 1
 
 
-def run_pass(out, cfg, counters, steps, op="update", packets=0, align=128):
+def run_pass(out, cfg, counters, steps, op="update", packets=0, align=128, warmup=1, tail=0):
     """One rocprofv3 pass with the given counters; per counter, the sum over the op's kernels of the
     median over that kernel's dispatches of the counter per packet the dispatch covers (its grid size
     / work items per packet), times the call's packets. A call that runs as several sub-batches
     (nfcs_update_device above 512K long frames, the forward's deferred bursts) is so counted whole
     from the dispatches the trace holds, whatever the thresholds (the number of sub-batches
-    is no longer predicted here)."""
+    is no longer predicted here). tail > 0 keeps only the last `tail` dispatches of the op's kernels: the
+    steady state of a context whose form follows its last calls (the plain update's store policy turns
+    sparse only after the warm-up's calls have been observed; bench.py's warm-up syncs every 16 steps, so
+    --warmup 64 --tail <steps> counts calls in the settled form)."""
     d = os.path.join(out, f"c{cfg}{'_' + str(packets) if packets else ''}_a{align}_{op}_{counters[0]}")
     cmd = ["timeout", "-s", "KILL", "150", "rocprofv3", "--pmc", *counters, "--kernel-trace", "--output-format", "csv", "-d", d,
            "-o", "p", "--", sys.executable, os.path.join(ROOT, "bench.py"), "--config", str(cfg),
-           "--steps", str(steps), "--warmup", "1", "--warm-seconds", "0", "--no-cpu", "--no-replay", "--no-host", "--no-c4", "--op", op, "--align", str(align)] + (["--packets", str(packets)] if packets else [])
+           "--steps", str(steps), "--warmup", str(warmup), "--warm-seconds", "0", "--no-cpu", "--no-replay", "--no-host", "--no-c4", "--op", op, "--align", str(align)] + (["--packets", str(packets)] if packets else [])
     env = dict(os.environ, TMPDIR="/tmp")
     r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=300)
     if r.returncode != 0:
@@ -62,7 +65,12 @@ def run_pass(out, cfg, counters, steps, op="update", packets=0, align=128):
     for root, _, files in os.walk(d):
         for f in files:
             if f.endswith("counter_collection.csv"):
-                for row in csv.DictReader(open(os.path.join(root, f))):
+                rows = [r for r in csv.DictReader(open(os.path.join(root, f)))
+                        if any(k in r["Kernel_Name"] for k in KERNEL[op])]
+                if tail:
+                    ids = sorted({int(r["Dispatch_Id"]) for r in rows})[-tail:]
+                    rows = [r for r in rows if int(r["Dispatch_Id"]) >= ids[0]]
+                for row in rows:
                     for k in KERNEL[op]:
                         if k in row["Kernel_Name"] and (k, row["Counter_Name"]) in vals:
                             pk = int(row["Grid_Size"]) / threads_per_packet(row["Kernel_Name"])
@@ -87,6 +95,8 @@ def main():
     ap.add_argument("--packets", type=int, default=0,
                     help="packets per launch instead of the config's (C1 with 4194304 = the C4 shard)")
     ap.add_argument("--align", type=int, default=128, help="frame start alignment (bench.py --align)")
+    ap.add_argument("--warmup", type=int, default=1, help="bench.py --warmup")
+    ap.add_argument("--tail", type=int, default=0, help="count only the last N dispatches of the op's kernels")
     a = ap.parse_args()
     a.out = os.path.abspath(a.out)  # rocprofv3 runs with cwd /tmp
     os.makedirs(a.out, exist_ok=True)
@@ -99,11 +109,12 @@ def main():
         res = json.load(open(a.merge))
     for cfg, op in [(c, o) for o in a.ops for c in a.configs]:
         P = a.packets
-        f, nf_, sub = run_pass(a.out, cfg, ["FETCH_SIZE"], a.steps, op, P, a.align)
-        w, nw, _ = run_pass(a.out, cfg, ["WRITE_SIZE"], a.steps, op, P, a.align)
+        wt = (a.warmup, a.tail)
+        f, nf_, sub = run_pass(a.out, cfg, ["FETCH_SIZE"], a.steps, op, P, a.align, *wt)
+        w, nw, _ = run_pass(a.out, cfg, ["WRITE_SIZE"], a.steps, op, P, a.align, *wt)
         q, _, _ = run_pass(a.out, cfg, ["TCC_BUBBLE_sum", "TCC_EA0_RDREQ_sum", "TCC_EA0_RDREQ_32B_sum"],
-                           a.steps, op, P, a.align)
-        wq, _, _ = run_pass(a.out, cfg, ["TCC_EA0_WRREQ_sum", "TCC_EA0_WRREQ_64B_sum"], a.steps, op, P, a.align)
+                           a.steps, op, P, a.align, *wt)
+        wq, _, _ = run_pass(a.out, cfg, ["TCC_EA0_WRREQ_sum", "TCC_EA0_WRREQ_64B_sum"], a.steps, op, P, a.align, *wt)
         key = ("C4_shard" if (cfg == 1 and P == 1 << 22) else f"C{cfg}" + (f"_{P}" if P else "")) + \
             ("" if op == "update" else f"_{op}") + ("" if a.align == 128 else f"_align{a.align}")
         fb, wb = 2 * f["FETCH_SIZE"] * 1024, w["WRITE_SIZE"] * 1024
