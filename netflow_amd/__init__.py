@@ -150,6 +150,7 @@ _lib = None
 _vp = ctypes.c_void_p
 _u32 = ctypes.c_uint32
 _u64 = ctypes.c_uint64
+_TABLES = ("fib", "acl", "fdb", "icmp", "egress", "aclset")
 
 
 def _declare(L):
@@ -199,34 +200,22 @@ def _declare(L):
         "nfcs_time_l3_forward_device": ([_vp, _vp, _u64, _vp, _vp, _u32, _vp, _u32, _vp,
                                          ctypes.c_int, _vp, ctypes.POINTER(ctypes.c_float)],
                                         ctypes.c_int),
-        "nfcs_fib_create": ([ctypes.POINTER(_vp)], ctypes.c_int),
-        "nfcs_fib_destroy": ([_vp], ctypes.c_int),
         "nfcs_fib_set_routes": ([_vp, _vp, _u32], ctypes.c_int),
         "nfcs_fib_set_arp": ([_vp, _vp, _u32], ctypes.c_int),
         "nfcs_fib_set_if_macs": ([_vp, _vp, _u32], ctypes.c_int),
         "nfcs_fib_set_local_ips": ([_vp, _vp, _u32], ctypes.c_int),
-        "nfcs_fib_commit": ([_vp], ctypes.c_int),
-        "nfcs_fib_upload": ([_vp, _vp], ctypes.c_int),
         "nfcs_fib_nexthops": ([_vp, ctypes.POINTER(_vp), ctypes.POINTER(_u32)], ctypes.c_int),
         "nfcs_fib_nexthops_host": ([_vp, _vp, _u32, ctypes.POINTER(_u32)], ctypes.c_int),
         "nfcs_fib_lookup_host": ([_vp, _u32, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32),
                                   ctypes.POINTER(_u32)], ctypes.c_int),
         "nfcs_route_lookup_device": ([_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp], ctypes.c_int),
-        "nfcs_acl_create": ([ctypes.POINTER(_vp)], ctypes.c_int),
-        "nfcs_acl_destroy": ([_vp], ctypes.c_int),
         "nfcs_acl_set_rules": ([_vp, _vp, _u32], ctypes.c_int),
-        "nfcs_acl_commit": ([_vp], ctypes.c_int),
-        "nfcs_acl_upload": ([_vp, _vp], ctypes.c_int),
         "nfcs_acl_eval_host": ([_vp, _vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32),
                                 ctypes.POINTER(_u32)], ctypes.c_int),
         "nfcs_acl_eval_device": ([_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
-        "nfcs_fdb_create": ([ctypes.POINTER(_vp)], ctypes.c_int),
-        "nfcs_fdb_destroy": ([_vp], ctypes.c_int),
         "nfcs_fdb_set_entries": ([_vp, _vp, _u32], ctypes.c_int),
         "nfcs_fdb_set_port": ([_vp, _vp, _vp, _u32], ctypes.c_int),
         "nfcs_fdb_clear_ports": ([_vp], ctypes.c_int),
-        "nfcs_fdb_commit": ([_vp], ctypes.c_int),
-        "nfcs_fdb_upload": ([_vp, _vp], ctypes.c_int),
         "nfcs_fdb_stats": ([_vp] + [ctypes.POINTER(_u32)] * 4, ctypes.c_int),
         "nfcs_fdb_lookup_host": ([_vp, _u32, _vp, _u32] + [ctypes.POINTER(_u32)] * 4, ctypes.c_int),
         "nfcs_fdb_flood_ports_host": ([_vp, _u32, _u32, _u32, _vp, _u32, ctypes.POINTER(_u32)], ctypes.c_int),
@@ -236,38 +225,26 @@ def _declare(L):
                                      [_vp] * 5, ctypes.c_int),
         "nfcs_flood_expand_host": ([_vp, _u32, _u32, _u64, _u64, _u32, _vp, _u32] + [_vp] * 5 + [_u32] + [_vp] * 4,
                                    ctypes.c_int),
-        "nfcs_icmp_create": ([ctypes.POINTER(_vp)], ctypes.c_int),
-        "nfcs_icmp_destroy": ([_vp], ctypes.c_int),
         "nfcs_icmp_set_local": ([_vp, _vp, _u32], ctypes.c_int),
         "nfcs_icmp_set_if_ips": ([_vp, _vp, _u32], ctypes.c_int),
         "nfcs_icmp_set_ports_up": ([_vp, _vp, _u32, _u32], ctypes.c_int),
-        "nfcs_icmp_commit": ([_vp], ctypes.c_int),
-        "nfcs_icmp_upload": ([_vp, _vp], ctypes.c_int),
         "nfcs_fib_resolve_host": ([_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32)],
                                   ctypes.c_int),
         "nfcs_icmp_respond_device": ([_vp, _vp, _vp, _u32, _vp, _u64, _u64, _u32, _vp, _u32, _vp, _vp, _u32] +
                                      [_vp] * 6, ctypes.c_int),
         "nfcs_icmp_respond_host": ([_vp, _vp, _u32, _vp, _u64, _u64, _u32, _vp, _u32, _vp, _vp, _u32] + [_vp] * 5,
                                    ctypes.c_int),
-        "nfcs_egress_create": ([ctypes.POINTER(_vp)], ctypes.c_int),
-        "nfcs_egress_destroy": ([_vp], ctypes.c_int),
         "nfcs_egress_set_port": ([_vp, _vp], ctypes.c_int),
         "nfcs_egress_clear_ports": ([_vp], ctypes.c_int),
-        "nfcs_egress_commit": ([_vp], ctypes.c_int),
-        "nfcs_egress_upload": ([_vp, _vp], ctypes.c_int),
         "nfcs_egress_keys": ([_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)], ctypes.c_int),
         "nfcs_egress_plan_host": ([_vp, _u32, _vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32)], ctypes.c_int),
         "nfcs_egress_enqueue_host": ([_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
         "nfcs_egress_plan_device": ([_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
         "nfcs_egress_enqueue_device": ([_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
-        "nfcs_aclset_create": ([ctypes.POINTER(_vp)], ctypes.c_int),
-        "nfcs_aclset_destroy": ([_vp], ctypes.c_int),
         "nfcs_aclset_set_list": ([_vp, _u32, _vp, _u32], ctypes.c_int),
         "nfcs_aclset_remove_list": ([_vp, _u32], ctypes.c_int),
         "nfcs_aclset_bind_port": ([_vp, _u32, _u32], ctypes.c_int),
         "nfcs_aclset_clear": ([_vp], ctypes.c_int),
-        "nfcs_aclset_commit": ([_vp], ctypes.c_int),
-        "nfcs_aclset_upload": ([_vp, _vp], ctypes.c_int),
         "nfcs_aclset_info": ([_vp] + [ctypes.POINTER(_u32)] * 3, ctypes.c_int),
         "nfcs_aclset_eval_host": ([_vp, _u32, _vp, _u32] + [ctypes.POINTER(_u32)] * 3, ctypes.c_int),
         "nfcs_egress_acl_host": ([_vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
@@ -285,6 +262,9 @@ def _declare(L):
         "nfcs_txq_dequeue_host": ([_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp], ctypes.c_int),
         "nfcs_txq_closed_form_host": ([_u32, _u32, _u32, _vp, _u32, _vp, ctypes.POINTER(_u32), _vp, _u32], ctypes.c_int),
     }
+    for t in _TABLES:  # the life cycle every table object shares
+        sig.update({f"nfcs_{t}_create": ([ctypes.POINTER(_vp)], ctypes.c_int), f"nfcs_{t}_destroy": ([_vp], ctypes.c_int),
+                    f"nfcs_{t}_commit": ([_vp], ctypes.c_int), f"nfcs_{t}_upload": ([_vp, _vp], ctypes.c_int)})
     for name, (args, res) in sig.items():
         # a measurement build of an earlier round (NFCS_LIB, A/B runs) may lack a later entry point;
         # the product library exports every one (tests/test_abi.py)
@@ -342,44 +322,81 @@ def ip4(a: str) -> int:
     return int.from_bytes(bytes(int(x) for x in a.split(".")), "little")
 
 
-class Fib:
-    """The forwarding table behind Engine.route_lookup_device (nfcs_fib): routes in lookup order (the
-    first match wins: pass RoutingManager::get_routing_table() as it is), ARP entries, interface MACs
-    and the switch's own addresses. Addresses are u32 in network byte order (ip4())."""
+class _Handle:
+    """One C object nfcs_<_c>_*: `ptr` until close() destroys it, once; a half-built one has no ptr."""
+    _c = ""
+    ptr = None
+
+    def _call(self, fn, *args):
+        """nfcs_<_c>_<fn>(ptr, *args), checked."""
+        name = f"nfcs_{self._c}_{fn}"
+        _check(getattr(lib(), name)(self.ptr, *args), name)
+        return self
+
+    def close(self):
+        if self.ptr:
+            getattr(lib(), f"nfcs_{self._c}_destroy")(self.ptr)
+            self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Table(_Handle):
+    """A table object: setters, then commit() (compile), then upload(engine) (snapshot to its device). A
+    setter invalidates the commit, not the device copy, which stays as it is until the next upload."""
 
     def __init__(self):
         p = _vp()
-        _check(lib().nfcs_fib_create(ctypes.byref(p)), "nfcs_fib_create")
+        _check(getattr(lib(), f"nfcs_{self._c}_create")(ctypes.byref(p)), f"nfcs_{self._c}_create")
         self.ptr = p.value
 
-    def _set(self, fn, arr, dtype):
+    def _set_array(self, fn, arr, dtype, head=(), tail=()):
+        """The setters that pass one array: nfcs_<_c>_<fn>(ptr, *head, records, count, *tail)."""
         arr = np.ascontiguousarray(arr, dtype=dtype)
-        _check(getattr(lib(), fn)(self.ptr, arr.ctypes.data if len(arr) else None, len(arr)), fn)
+        return self._call(fn, *head, arr.ctypes.data if len(arr) else None, len(arr), *tail)
+
+    def commit(self):
+        return self._call("commit")
+
+    def upload(self, engine: "Engine"):
+        _check(getattr(lib(), f"nfcs_{self._c}_upload")(engine.ctx, self.ptr), f"nfcs_{self._c}_upload")
         return self
+
+
+class Fib(_Table):
+    """The forwarding table behind Engine.route_lookup_device (nfcs_fib): routes in lookup order (the
+    first match wins: pass RoutingManager::get_routing_table() as it is), ARP entries, interface MACs
+    and the switch's own addresses. Addresses are u32 in network byte order (ip4())."""
+    _c = "fib"
 
     def set_routes(self, routes):
         """FIB_ROUTE_DTYPE records {network, mask, next_hop_ip, egress_if}, in lookup order."""
-        return self._set("nfcs_fib_set_routes", routes, FIB_ROUTE_DTYPE)
+        return self._set_array("set_routes", routes, FIB_ROUTE_DTYPE)
 
     def set_arp(self, arp):
         """FIB_ARP_DTYPE records {ip, mac}; of duplicates the last one wins."""
-        return self._set("nfcs_fib_set_arp", arp, FIB_ARP_DTYPE)
+        return self._set_array("set_arp", arp, FIB_ARP_DTYPE)
 
     def set_if_macs(self, if_macs):
         """FIB_IF_MAC_DTYPE records {egress_if, mac}."""
-        return self._set("nfcs_fib_set_if_macs", if_macs, FIB_IF_MAC_DTYPE)
+        return self._set_array("set_if_macs", if_macs, FIB_IF_MAC_DTYPE)
 
     def set_local_ips(self, ips):
-        return self._set("nfcs_fib_set_local_ips", ips, np.dtype("<u4"))
-
-    def commit(self):
-        _check(lib().nfcs_fib_commit(self.ptr), "nfcs_fib_commit")
-        return self
+        return self._set_array("set_local_ips", ips, np.dtype("<u4"))
 
     def upload(self, engine: "Engine"):
         """Copy the committed tables to the engine's device; close the Fib before the engine."""
-        _check(lib().nfcs_fib_upload(engine.ctx, self.ptr), "nfcs_fib_upload")
-        return self
+        return super().upload(engine)
 
     def nexthops(self) -> tuple[int, int]:
         """(device pointer, entries) of the uploaded next-hop table, for l3_forward_device."""
@@ -414,50 +431,21 @@ class Fib:
                "nfcs_fib_resolve_host")
         return int(v.value), int(h.value), int(e.value)
 
-    def close(self):
-        if getattr(self, "ptr", None):
-            lib().nfcs_fib_destroy(self.ptr)
-            self.ptr = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Acl:
+class Acl(_Table):
     """One ACL rule list behind Engine.acl_eval_device (nfcs_acl): ACL_RULE_DTYPE records scanned in the
     order given, the first match decides (pass AclManager::get_all_rules(name) as it is), no match
     permits. Addresses and their masks are u32 in HOST byte order (10.1.2.3 = 0x0A010203), as AclRule
     holds them, unlike the Fib's network-order ones."""
-
-    def __init__(self):
-        p = _vp()
-        _check(lib().nfcs_acl_create(ctypes.byref(p)), "nfcs_acl_create")
-        self.ptr = p.value
+    _c = "acl"
 
     def set_rules(self, rules):
         """ACL_RULE_DTYPE records, in scan order; at most ACL_MAX_RULES."""
-        rules = np.ascontiguousarray(rules, dtype=ACL_RULE_DTYPE)
-        _check(lib().nfcs_acl_set_rules(self.ptr, rules.ctypes.data if len(rules) else None, len(rules)),
-               "nfcs_acl_set_rules")
-        return self
-
-    def commit(self):
-        _check(lib().nfcs_acl_commit(self.ptr), "nfcs_acl_commit")
-        return self
+        return self._set_array("set_rules", rules, ACL_RULE_DTYPE)
 
     def upload(self, engine: "Engine"):
         """Copy the committed rules to the engine's device; close the Acl before the engine."""
-        _check(lib().nfcs_acl_upload(engine.ctx, self.ptr), "nfcs_acl_upload")
-        return self
+        return super().upload(engine)
 
     def eval_host(self, frame: bytes) -> tuple[int, int, int]:
         """(action, index of the deciding rule or ACL_NO_MATCH, redirect port or IF_NONE) for one frame,
@@ -468,64 +456,32 @@ class Acl:
                                         ctypes.byref(r), ctypes.byref(p)), "nfcs_acl_eval_host")
         return int(a.value), int(r.value), int(p.value)
 
-    def close(self):
-        if getattr(self, "ptr", None):
-            lib().nfcs_acl_destroy(self.ptr)
-            self.ptr = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class AclSet:
+class AclSet(_Table):
     """The egress ACLs behind Engine.egress_acl_device (nfcs_aclset): rule lists by id (0..ACLSET_MAX_LISTS-1,
     ACL_RULE_DTYPE records as in Acl) and port -> list bindings. A port that is unbound, bound to a list that
     was never set or was removed, or bound to an empty list has no list: every frame is permitted unread.
     All non-empty lists together, each padded to ACL_GROUP, hold at most ACL_MAX_RULES rules (commit)."""
-
-    def __init__(self):
-        p = _vp()
-        _check(lib().nfcs_aclset_create(ctypes.byref(p)), "nfcs_aclset_create")
-        self.ptr = p.value
+    _c = "aclset"
 
     def set_list(self, list_id: int, rules):
         """Replace list list_id; no rules is an existing, empty list."""
-        rules = np.ascontiguousarray(rules, dtype=ACL_RULE_DTYPE)
-        _check(lib().nfcs_aclset_set_list(self.ptr, int(list_id), rules.ctypes.data if len(rules) else None,
-                                          len(rules)), "nfcs_aclset_set_list")
-        return self
+        return self._set_array("set_list", rules, ACL_RULE_DTYPE, head=(int(list_id),))
 
     def remove_list(self, list_id: int):
         """AclManager::delete_acl: bindings to the list stay and read "no list"."""
-        _check(lib().nfcs_aclset_remove_list(self.ptr, int(list_id)), "nfcs_aclset_remove_list")
-        return self
+        return self._call("remove_list", int(list_id))
 
     def bind_port(self, port_id: int, list_id: int):
         """apply_acl_to_interface(port, list, EGRESS); ACL_LIST_NONE unbinds."""
-        _check(lib().nfcs_aclset_bind_port(self.ptr, int(port_id), int(list_id)), "nfcs_aclset_bind_port")
-        return self
+        return self._call("bind_port", int(port_id), int(list_id))
 
     def clear(self):
-        _check(lib().nfcs_aclset_clear(self.ptr), "nfcs_aclset_clear")
-        return self
-
-    def commit(self):
-        _check(lib().nfcs_aclset_commit(self.ptr), "nfcs_aclset_commit")
-        return self
+        return self._call("clear")
 
     def upload(self, engine: "Engine"):
         """Copy the committed arrays to the engine's device; close the AclSet before the engine."""
-        _check(lib().nfcs_aclset_upload(engine.ctx, self.ptr), "nfcs_aclset_upload")
-        return self
+        return super().upload(engine)
 
     def info(self) -> tuple[int, int, int]:
         """(ports = highest bound port id + 1, lists laid out, their padded rule total)."""
@@ -562,41 +518,17 @@ class AclSet:
                                           cp(denied_pkts), cp(denied_bytes)), "nfcs_egress_acl_host")
         return {"port": port, "action": action, "rule": rule, "redirect": redirect}
 
-    def close(self):
-        if getattr(self, "ptr", None):
-            lib().nfcs_aclset_destroy(self.ptr)
-            self.ptr = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Fdb:
+class Fdb(_Table):
     """The L2 forwarding database and port state behind Engine.l2_lookup_device (nfcs_fdb): FDB_ENTRY_DTYPE
     records (pass ForwardingDatabase::get_all_entries() as it is; of two with one (mac, vlan_id) the first
     wins), compiled into an open-addressing hash table, and one L2_PORT_DTYPE record plus allowed VLANs per
     port. A port never set is link down, STP unknown, without a VLAN config."""
-
-    def __init__(self):
-        p = _vp()
-        _check(lib().nfcs_fdb_create(ctypes.byref(p)), "nfcs_fdb_create")
-        self.ptr = p.value
+    _c = "fdb"
 
     def set_entries(self, entries):
         """FDB_ENTRY_DTYPE records; at most FDB_MAX_ENTRIES."""
-        entries = np.ascontiguousarray(entries, dtype=FDB_ENTRY_DTYPE)
-        _check(lib().nfcs_fdb_set_entries(self.ptr, entries.ctypes.data if len(entries) else None, len(entries)),
-               "nfcs_fdb_set_entries")
-        return self
+        return self._set_array("set_entries", entries, FDB_ENTRY_DTYPE)
 
     def set_port(self, port_id: int, link_up=True, stp_forwarding=True, has_vlan_config=True, type=L2_ACCESS,
                  native_vlan: int = 1, allowed_vlans=()):
@@ -604,23 +536,14 @@ class Fdb:
         rec = np.zeros(1, dtype=L2_PORT_DTYPE)
         rec["port_id"], rec["link_up"], rec["stp_forwarding"] = port_id, bool(link_up), bool(stp_forwarding)
         rec["has_vlan_config"], rec["type"], rec["native_vlan"] = bool(has_vlan_config), type, native_vlan
-        allowed = np.ascontiguousarray(list(allowed_vlans), dtype=np.uint16)
-        _check(lib().nfcs_fdb_set_port(self.ptr, rec.ctypes.data, allowed.ctypes.data if len(allowed) else None,
-                                       len(allowed)), "nfcs_fdb_set_port")
-        return self
+        return self._set_array("set_port", list(allowed_vlans), np.uint16, head=(rec.ctypes.data,))
 
     def clear_ports(self):
-        _check(lib().nfcs_fdb_clear_ports(self.ptr), "nfcs_fdb_clear_ports")
-        return self
-
-    def commit(self):
-        _check(lib().nfcs_fdb_commit(self.ptr), "nfcs_fdb_commit")
-        return self
+        return self._call("clear_ports")
 
     def upload(self, engine: "Engine"):
         """Copy the committed tables to the engine's device; close the Fdb before the engine."""
-        _check(lib().nfcs_fdb_upload(engine.ctx, self.ptr), "nfcs_fdb_upload")
-        return self
+        return super().upload(engine)
 
     def stats(self) -> dict:
         """The committed table: entries (distinct keys), slots, max_probe (longest displacement + 1) and
@@ -674,64 +597,29 @@ class Fdb:
                "nfcs_flood_expand_host")
         return {"item_desc": item_desc, "item_port": item_port, "item_src": item_src, "totals": totals[0]}
 
-    def close(self):
-        if getattr(self, "ptr", None):
-            lib().nfcs_fdb_destroy(self.ptr)
-            self.ptr = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Icmp:
+class Icmp(_Table):
     """The tables behind Engine.icmp_respond_device (nfcs_icmp): the switch's own addresses with their MACs
     (get_mac_for_ip), each interface's first address (get_interface_ip) and the ports that are up
     (send_control_plane_packet's test). Addresses are u32 in network byte order, as in Fib; of duplicates the
     first wins. Routes, ARP and interface MACs come from the Fib given to the call."""
-
-    def __init__(self):
-        p = _vp()
-        _check(lib().nfcs_icmp_create(ctypes.byref(p)), "nfcs_icmp_create")
-        self.ptr = p.value
+    _c = "icmp"
 
     def set_local(self, local):
         """ICMP_LOCAL_DTYPE records {ip, mac}."""
-        local = np.ascontiguousarray(local, dtype=ICMP_LOCAL_DTYPE)
-        _check(lib().nfcs_icmp_set_local(self.ptr, local.ctypes.data if len(local) else None, len(local)),
-               "nfcs_icmp_set_local")
-        return self
+        return self._set_array("set_local", local, ICMP_LOCAL_DTYPE)
 
     def set_if_ips(self, if_ips):
         """ICMP_IF_IP_DTYPE records {egress_if, ip}."""
-        if_ips = np.ascontiguousarray(if_ips, dtype=ICMP_IF_IP_DTYPE)
-        _check(lib().nfcs_icmp_set_if_ips(self.ptr, if_ips.ctypes.data if len(if_ips) else None, len(if_ips)),
-               "nfcs_icmp_set_if_ips")
-        return self
+        return self._set_array("set_if_ips", if_ips, ICMP_IF_IP_DTYPE)
 
     def set_ports_up(self, ports, num_ports: int):
         """The ports below num_ports whose link is up."""
-        ports = np.ascontiguousarray(ports, dtype=np.uint32)
-        _check(lib().nfcs_icmp_set_ports_up(self.ptr, ports.ctypes.data if len(ports) else None, len(ports),
-                                            int(num_ports)), "nfcs_icmp_set_ports_up")
-        return self
-
-    def commit(self):
-        _check(lib().nfcs_icmp_commit(self.ptr), "nfcs_icmp_commit")
-        return self
+        return self._set_array("set_ports_up", ports, np.uint32, tail=(int(num_ports),))
 
     def upload(self, engine: "Engine"):
         """Copy the committed tables to the engine's device; close the Icmp before the engine."""
-        _check(lib().nfcs_icmp_upload(engine.ctx, self.ptr), "nfcs_icmp_upload")
-        return self
+        return super().upload(engine)
 
     def respond_host(self, fib: "Fib", ingress_port: int, arena, msg_base: int, msg_align: int, desc, rt_verdict,
                      cap: int, ip_id=None) -> dict:
@@ -757,34 +645,13 @@ class Icmp:
                                             totals.ctypes.data), "nfcs_icmp_respond_host")
         return {"msg_desc": msg_desc, "msg_port": msg_port, "msg_src": msg_src, "status": status, "totals": totals[0]}
 
-    def close(self):
-        if getattr(self, "ptr", None):
-            lib().nfcs_icmp_destroy(self.ptr)
-            self.ptr = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Egress:
+class Egress(_Table):
     """The egress ports behind Engine.egress_plan_device / egress_enqueue_device (nfcs_egress): one
     EGRESS_PORT_DTYPE record per port, holding what VlanManager::process_egress and QosManager::enqueue_packet
     read of it. A port never set has no VLAN config and no QoS config. The (port, queue) pair is the key
     port * QOS_MAX_QUEUES + queue."""
-
-    def __init__(self):
-        p = _vp()
-        _check(lib().nfcs_egress_create(ctypes.byref(p)), "nfcs_egress_create")
-        self.ptr = p.value
+    _c = "egress"
 
     def set_port(self, port_id: int, has_vlan_config=True, type=L2_ACCESS, tag_native=False, native_vlan: int = 1,
                  has_qos=True, num_queues: int = 4, max_queue_depth: int = 1000):
@@ -797,21 +664,14 @@ class Egress:
                 raise NfcsError(f"nfcs_egress_set_port: {name} = {v} does not fit its field")
             rec[name] = int(v)
         rec["has_vlan_config"], rec["tag_native"], rec["has_qos"] = bool(has_vlan_config), bool(tag_native), bool(has_qos)
-        _check(lib().nfcs_egress_set_port(self.ptr, rec.ctypes.data), "nfcs_egress_set_port")
-        return self
+        return self._call("set_port", rec.ctypes.data)
 
     def clear_ports(self):
-        _check(lib().nfcs_egress_clear_ports(self.ptr), "nfcs_egress_clear_ports")
-        return self
-
-    def commit(self):
-        _check(lib().nfcs_egress_commit(self.ptr), "nfcs_egress_commit")
-        return self
+        return self._call("clear_ports")
 
     def upload(self, engine: "Engine"):
         """Copy the committed records to the engine's device; close the Egress before the engine."""
-        _check(lib().nfcs_egress_upload(engine.ctx, self.ptr), "nfcs_egress_upload")
-        return self
+        return super().upload(engine)
 
     def keys(self) -> tuple[int, int]:
         """(ports, keys) of the committed table: keys = ports * QOS_MAX_QUEUES."""
@@ -847,29 +707,13 @@ class Egress:
         return {"depth": depth, "result": result, "order": order[:int(key_start[keys])], "key_start": key_start,
                 "key_dropped": key_dropped}
 
-    def close(self):
-        if getattr(self, "ptr", None):
-            lib().nfcs_egress_destroy(self.ptr)
-            self.ptr = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class TxQueues:
+class TxQueues(_Handle):
     """The TX queues of a committed Egress (nfcs_txq): one ring of 64-bit handles per (port, queue) and the
     scheduler of QosManager::select_packet_to_dequeue. With an engine it holds a device copy beside the host
     copy (Engine.txq_append_device / txq_dequeue_device advance it); without one it is host-only. It
     snapshots the Egress at creation; close it before the engine."""
+    _c = "txq"
 
     def __init__(self, egress: "Egress", engine: "Engine | None" = None):
         p = _vp()
@@ -882,13 +726,11 @@ class TxQueues:
         """QosConfig::scheduler of one port (SCHED_*; default SCHED_STRICT_PRIORITY), on both copies."""
         if not (0 <= int(port_id) <= 0xFFFFFFFF and 0 <= int(sched) <= 0xFFFFFFFF):
             raise NfcsError("nfcs_txq_set_scheduler: invalid argument")
-        _check(lib().nfcs_txq_set_scheduler(self.ptr, int(port_id), int(sched)), "nfcs_txq_set_scheduler")
-        return self
+        return self._call("set_scheduler", int(port_id), int(sched))
 
     def reset(self):
         """Heads and last-serviced queues to 0 on both copies (configure_port_qos)."""
-        _check(lib().nfcs_txq_reset(self.ptr), "nfcs_txq_reset")
-        return self
+        return self._call("reset")
 
     def info(self) -> tuple[int, int, int]:
         """(ports, keys, ring_slots)."""
@@ -948,23 +790,6 @@ class TxQueues:
         total = int(tx_start[self.ports])
         return {"depth": depth, "tx": tx[:total], "tx_queue": tx_queue[:total], "tx_start": tx_start,
                 "dequeued": dequeued}
-
-    def close(self):
-        if getattr(self, "ptr", None):
-            lib().nfcs_txq_destroy(self.ptr)
-            self.ptr = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def txq_closed_form_host(sched: int, depth, last: int, budget: int, want_seq: bool = True):

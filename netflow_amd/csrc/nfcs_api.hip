@@ -20,6 +20,7 @@
 #include <mutex>
 #include <new>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "nfcs_internal.h"
@@ -921,6 +922,149 @@ int l3_forward_device(nfcs_ctx* c, uint8_t* d_arena, uint64_t arena_bytes, const
     return NFCS_OK;
 }
 
+// ---- the life cycle the six table objects share -------------------------------------
+// Setters change `in` and clear `committed`; commit compiles `in` into `t`; upload snapshots `t` into one
+// device allocation on `device`, which nothing but the next upload or the destroy changes.
+template <class In, class Tables, class Dev>
+struct Table {
+    In in;
+    Tables t;
+    bool committed = false;
+    int device = -1;
+    uint8_t* d_blob = nullptr;
+    Dev dev{};
+    bool uploaded = false;
+    void drop_upload() {
+        if (d_blob) {
+            DeviceGuard dg_(device);
+            if (dg_.err == hipSuccess) (void)hipFree(d_blob);
+        }
+        d_blob = nullptr;
+        dev = Dev{};
+        uploaded = false;
+    }
+};
+
+template <class T>
+int table_create(T** out) {
+    if (!out) return NFCS_EINVAL;
+    *out = new (std::nothrow) T();
+    return *out ? NFCS_OK : NFCS_ENOMEM;
+}
+template <class T>
+int table_destroy(T* t) {
+    if (!t) return NFCS_EINVAL;
+    t->drop_upload();
+    delete t;
+    return NFCS_OK;
+}
+
+// fn() as a return code: NFCS_OK for one that returns nothing, NFCS_ENOMEM for one that throws.
+template <class F>
+int guarded(F&& fn) {
+    try {
+        if constexpr (std::is_void_v<decltype(fn())>) {
+            fn();
+            return NFCS_OK;
+        } else {
+            return fn();
+        }
+    } catch (...) {
+        return NFCS_ENOMEM;
+    }
+}
+// A setter's change to t->in. A rejected one leaves the commit standing; after an accepted one the object is
+// uncommitted, and the device copy, if any, stays as it is until the next upload.
+template <class T, class F>
+int table_set(T* t, F&& fn) {
+    if (!t) return NFCS_EINVAL;
+    const int rc = guarded(fn);
+    if (rc == NFCS_OK) t->committed = false;
+    return rc;
+}
+// The setters that replace one input array.
+template <class T, class In, class V>
+int table_assign(T* t, std::vector<V> In::*field, const V* src, uint32_t n) {
+    if (!t || (n > 0 && !src)) return NFCS_EINVAL;
+    return table_set(t, [&] { (t->in.*field).assign(src, src + n); });
+}
+// compile(in, t): a table whose compile fails is uncommitted, since t may be half rebuilt.
+template <class T, class F>
+int table_commit(T* t, F&& compile) {
+    if (!t) return NFCS_EINVAL;
+    t->committed = false;
+    const int rc = guarded([&] { return compile(t->in, t->t); });
+    t->committed = rc == NFCS_OK;
+    return rc;
+}
+// A table the device entry points of context c may read.
+template <class T>
+bool usable(const nfcs_ctx* c, const T* t) {
+    return c && t && t->uploaded && t->device == c->di.device;
+}
+
+// One device allocation of several arrays, each on a 16-byte boundary, zero between and 16 bytes past them.
+struct BlobLayout {
+    static constexpr int kMaxParts = 8;
+    struct Part { const void* src; size_t bytes, off; };
+    Part parts[kMaxParts];
+    int n = 0;
+    size_t total = 0;
+    // Appends `bytes` bytes, copied from src where it is given (zero otherwise); returns their offset.
+    size_t part(const void* src, size_t bytes) {
+        const size_t at = total;
+        if (n < kMaxParts) parts[n] = {src, bytes, at};
+        ++n;
+        total += (bytes + 15u) & ~(size_t)15u;
+        return at;
+    }
+    template <class V>
+    size_t part(const std::vector<V>& v) { return part(v.data(), v.size() * sizeof(V)); }
+    // The caller has the owning device current. On an error *d_blob holds what was allocated, if anything.
+    hipError_t upload(uint8_t** d_blob) const {
+        if (n > kMaxParts) return hipErrorInvalidValue;
+        hipError_t e = hipMalloc(d_blob, total + 16u);
+        if (e == hipSuccess) e = hipMemset(*d_blob, 0, total + 16u);
+        for (int i = 0; i < n && e == hipSuccess; ++i)
+            if (parts[i].src && parts[i].bytes)
+                e = hipMemcpy(*d_blob + parts[i].off, parts[i].src, parts[i].bytes, hipMemcpyHostToDevice);
+        return e;
+    }
+};
+
+// Replaces t's device copy by the laid-out blob on c's device; bind(d_blob) fills t->dev from the offsets.
+// A failure leaves t without a device copy.
+template <class T, class Bind>
+int table_upload(nfcs_ctx* c, T* t, const BlobLayout& lay, Bind&& bind) {
+    t->drop_upload();
+    DeviceGuard dg_(c->di.device);
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    t->device = c->di.device;
+    const hipError_t e = lay.upload(&t->d_blob);
+    if (e != hipSuccess) {
+        t->drop_upload();
+        return hip_fail(e);
+    }
+    bind(t->d_blob);
+    t->uploaded = true;
+    return NFCS_OK;
+}
+
+// launch(scratch) on st with `words` words of the context's enqueue scratch (eq_ws), which the flood and the
+// ICMP stages use too. Without the memory the context stays usable: only this call's scratch is missing.
+template <class Launch>
+int with_eq_scratch(nfcs_ctx* c, uint64_t words, hipStream_t st, Launch&& launch) {
+    const hipError_t e = acquire_eq(c, words, st);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        return NFCS_ENOMEM;
+    }
+    NFCS_HIP(e);
+    NFCS_HIP(launch(c->eq_ws));
+    NFCS_HIP(release_eq(c, st));
+    return NFCS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1108,125 +1252,56 @@ NFCS_API int nfcs_flow_keys_device(nfcs_ctx* c, const uint8_t* d_arena, uint64_t
 // ---- forwarding table (nfcs_fib.h: inputs, commit, host decision) and its lookup kernel ----------
 }  // extern "C"
 
-struct nfcs_fib {
-    nfcs::FibInputs in;
-    nfcs::FibTables t;
-    bool committed = false;
-    // nfcs_fib_upload: one device allocation holding every array, on `device`
-    int device = -1;
-    uint8_t* d_blob = nullptr;
-    nfcs::FibDev dev;
+struct nfcs_fib : Table<nfcs::FibInputs, nfcs::FibTables, nfcs::FibDev> {
     const nfcs_nexthop* d_table = nullptr;
     uint32_t d_table_n = 0;  // the table as uploaded (a later commit does not change it)
-    bool uploaded = false;
+    void drop_upload() {
+        Table::drop_upload();
+        d_table = nullptr;
+        d_table_n = 0;
+    }
 };
-
-namespace {
-void fib_drop_upload(nfcs_fib* f) {
-    if (f->d_blob) {
-        DeviceGuard dg_(f->device);
-        if (dg_.err == hipSuccess) (void)hipFree(f->d_blob);
-    }
-    f->d_blob = nullptr;
-    f->dev = nfcs::FibDev{};
-    f->d_table = nullptr;
-    f->d_table_n = 0;
-    f->uploaded = false;
-}
-template <class T>
-int fib_set(nfcs_fib* f, std::vector<T>& dst, const T* src, uint32_t n) {
-    if (!f || (n > 0 && !src)) return NFCS_EINVAL;
-    try {
-        dst.assign(src, src + n);
-    } catch (...) {
-        return NFCS_ENOMEM;
-    }
-    f->committed = false;  // the device copy, if any, stays as it is until the next upload
-    return NFCS_OK;
-}
-}  // namespace
 
 extern "C" {
 
-NFCS_API int nfcs_fib_create(nfcs_fib** out) {
-    if (!out) return NFCS_EINVAL;
-    *out = new (std::nothrow) nfcs_fib();
-    return *out ? NFCS_OK : NFCS_ENOMEM;
-}
-
-NFCS_API int nfcs_fib_destroy(nfcs_fib* f) {
-    if (!f) return NFCS_EINVAL;
-    fib_drop_upload(f);
-    delete f;
-    return NFCS_OK;
-}
+NFCS_API int nfcs_fib_create(nfcs_fib** out) { return table_create(out); }
+NFCS_API int nfcs_fib_destroy(nfcs_fib* f) { return table_destroy(f); }
 
 NFCS_API int nfcs_fib_set_routes(nfcs_fib* f, const nfcs_fib_route* routes, uint32_t n) {
     if (n > NFCS_FIB_MAX_ROUTES) return NFCS_EINVAL;
-    return f ? fib_set(f, f->in.routes, routes, n) : NFCS_EINVAL;
+    return table_assign(f, &nfcs::FibInputs::routes, routes, n);
 }
 NFCS_API int nfcs_fib_set_arp(nfcs_fib* f, const nfcs_fib_arp* arp, uint32_t n) {
-    return f ? fib_set(f, f->in.arp, arp, n) : NFCS_EINVAL;
+    return table_assign(f, &nfcs::FibInputs::arp, arp, n);
 }
 NFCS_API int nfcs_fib_set_if_macs(nfcs_fib* f, const nfcs_fib_if_mac* if_macs, uint32_t n) {
-    return f ? fib_set(f, f->in.if_macs, if_macs, n) : NFCS_EINVAL;
+    return table_assign(f, &nfcs::FibInputs::if_macs, if_macs, n);
 }
 NFCS_API int nfcs_fib_set_local_ips(nfcs_fib* f, const uint32_t* ips, uint32_t n) {
-    return f ? fib_set(f, f->in.local_ips, ips, n) : NFCS_EINVAL;
+    return table_assign(f, &nfcs::FibInputs::local_ips, ips, n);
 }
 
-NFCS_API int nfcs_fib_commit(nfcs_fib* f) {
-    if (!f) return NFCS_EINVAL;
-    try {
-        nfcs::fib_compile(f->in, f->t);
-    } catch (...) {
-        return NFCS_ENOMEM;
-    }
-    f->committed = true;
-    return NFCS_OK;
-}
+NFCS_API int nfcs_fib_commit(nfcs_fib* f) { return table_commit(f, nfcs::fib_compile); }
 
 NFCS_API int nfcs_fib_upload(nfcs_ctx* c, nfcs_fib* f) {
     if (!c || !f || !f->committed) return NFCS_EINVAL;
-    fib_drop_upload(f);
-    DeviceGuard dg_(c->di.device);
-    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
     const nfcs::FibTables& t = f->t;
-    // one blob, every array on a 16-byte boundary
-    auto up16 = [](size_t x) { return (x + 15u) & ~size_t(15); };
-    const size_t o_nm = 0, o_info = o_nm + up16(t.rt_nm.size() * 8u), o_aip = o_info + up16(t.rt_info.size() * 8u);
-    const size_t o_anh = o_aip + up16(t.arp_ip.size() * 4u), o_loc = o_anh + up16(t.arp_nh.size() * 4u);
-    const size_t o_tab = o_loc + up16(t.local_ip.size() * 4u), total = o_tab + up16(t.table.size() * sizeof(nfcs_nexthop));
-    std::vector<uint8_t> blob(total + 16u, 0);
-    auto put = [&](size_t o, const void* p, size_t bytes) {
-        if (bytes) memcpy(blob.data() + o, p, bytes);
-    };
-    put(o_nm, t.rt_nm.data(), t.rt_nm.size() * 8u);
-    put(o_info, t.rt_info.data(), t.rt_info.size() * 8u);
-    put(o_aip, t.arp_ip.data(), t.arp_ip.size() * 4u);
-    put(o_anh, t.arp_nh.data(), t.arp_nh.size() * 4u);
-    put(o_loc, t.local_ip.data(), t.local_ip.size() * 4u);
-    put(o_tab, t.table.data(), t.table.size() * sizeof(nfcs_nexthop));
-    NFCS_HIP(hipMalloc(&f->d_blob, blob.size()));
-    f->device = c->di.device;
-    const hipError_t e = hipMemcpy(f->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        fib_drop_upload(f);
-        return hip_fail(e);
-    }
-    f->dev.rt_nm = (const uint2*)(f->d_blob + o_nm);
-    f->dev.rt_info = (const uint2*)(f->d_blob + o_info);
-    f->dev.routes = t.routes;
-    f->dev.routes_padded = (uint32_t)t.rt_nm.size();
-    f->dev.arp_ip = (const uint32_t*)(f->d_blob + o_aip);
-    f->dev.arp_nh = (const uint32_t*)(f->d_blob + o_anh);
-    f->dev.arps = (uint32_t)t.arp_ip.size();
-    f->dev.local_ip = (const uint32_t*)(f->d_blob + o_loc);
-    f->dev.locals = (uint32_t)t.local_ip.size();
-    f->d_table = t.table.empty() ? nullptr : (const nfcs_nexthop*)(f->d_blob + o_tab);
-    f->d_table_n = (uint32_t)t.table.size();
-    f->uploaded = true;
-    return NFCS_OK;
+    BlobLayout lay;
+    const size_t o_nm = lay.part(t.rt_nm), o_info = lay.part(t.rt_info), o_aip = lay.part(t.arp_ip);
+    const size_t o_anh = lay.part(t.arp_nh), o_loc = lay.part(t.local_ip), o_tab = lay.part(t.table);
+    return table_upload(c, f, lay, [&](const uint8_t* d) {
+        f->dev.rt_nm = (const uint2*)(d + o_nm);
+        f->dev.rt_info = (const uint2*)(d + o_info);
+        f->dev.routes = t.routes;
+        f->dev.routes_padded = (uint32_t)t.rt_nm.size();
+        f->dev.arp_ip = (const uint32_t*)(d + o_aip);
+        f->dev.arp_nh = (const uint32_t*)(d + o_anh);
+        f->dev.arps = (uint32_t)t.arp_ip.size();
+        f->dev.local_ip = (const uint32_t*)(d + o_loc);
+        f->dev.locals = (uint32_t)t.local_ip.size();
+        f->d_table = t.table.empty() ? nullptr : (const nfcs_nexthop*)(d + o_tab);
+        f->d_table_n = (uint32_t)t.table.size();
+    });
 }
 
 NFCS_API int nfcs_fib_nexthops(const nfcs_fib* f, const nfcs_nexthop** d_table, uint32_t* table_n) {
@@ -1255,7 +1330,7 @@ NFCS_API int nfcs_route_lookup_device(nfcs_ctx* c, const nfcs_fib* f, const uint
                                       uint64_t arena_bytes, const nfcs_desc* d_desc, uint32_t n,
                                       uint32_t* d_nh, uint32_t* d_egress_if, uint8_t* d_verdict,
                                       void* stream) {
-    if (!c || !f || !f->uploaded || f->device != c->di.device) return NFCS_EINVAL;
+    if (!usable(c, f)) return NFCS_EINVAL;
     DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
     if (dg_.err != hipSuccess) return hip_fail(dg_.err);
     if (n == 0) return NFCS_OK;
@@ -1269,92 +1344,33 @@ NFCS_API int nfcs_route_lookup_device(nfcs_ctx* c, const nfcs_fib* f, const uint
 // ---- ACL (nfcs_acl.h: compile, host decision) and its evaluation kernel --------------------------
 }  // extern "C"
 
-struct nfcs_acl {
-    std::vector<nfcs_acl_rule> in;
-    nfcs::AclTables t;
-    bool committed = false;
-    // nfcs_acl_upload: one device allocation holding both arrays, on `device`
-    int device = -1;
-    uint8_t* d_blob = nullptr;
-    nfcs::AclDev dev;
-    bool uploaded = false;
-};
-
-namespace {
-void acl_drop_upload(nfcs_acl* a) {
-    if (a->d_blob) {
-        DeviceGuard dg_(a->device);
-        if (dg_.err == hipSuccess) (void)hipFree(a->d_blob);
-    }
-    a->d_blob = nullptr;
-    a->dev = nfcs::AclDev{};
-    a->uploaded = false;
-}
-}  // namespace
+struct nfcs_acl : Table<std::vector<nfcs_acl_rule>, nfcs::AclTables, nfcs::AclDev> {};
 
 extern "C" {
 
-NFCS_API int nfcs_acl_create(nfcs_acl** out) {
-    if (!out) return NFCS_EINVAL;
-    *out = new (std::nothrow) nfcs_acl();
-    return *out ? NFCS_OK : NFCS_ENOMEM;
-}
-
-NFCS_API int nfcs_acl_destroy(nfcs_acl* a) {
-    if (!a) return NFCS_EINVAL;
-    acl_drop_upload(a);
-    delete a;
-    return NFCS_OK;
-}
+NFCS_API int nfcs_acl_create(nfcs_acl** out) { return table_create(out); }
+NFCS_API int nfcs_acl_destroy(nfcs_acl* a) { return table_destroy(a); }
 
 NFCS_API int nfcs_acl_set_rules(nfcs_acl* a, const nfcs_acl_rule* rules, uint32_t n) {
     if (!a || (n > 0 && !rules) || n > NFCS_ACL_MAX_RULES) return NFCS_EINVAL;
     for (uint32_t i = 0; i < n; ++i)
         if ((rules[i].fields & ~NFCS_ACL_F_ALL) || rules[i].action > NFCS_ACL_REDIRECT) return NFCS_EINVAL;
-    try {
-        a->in.assign(rules, rules + n);
-    } catch (...) {
-        return NFCS_ENOMEM;
-    }
-    a->committed = false;  // the device copy, if any, stays as it is until the next upload
-    return NFCS_OK;
+    return table_set(a, [&] { a->in.assign(rules, rules + n); });
 }
 
-NFCS_API int nfcs_acl_commit(nfcs_acl* a) {
-    if (!a) return NFCS_EINVAL;
-    try {
-        nfcs::acl_compile(a->in, a->t);
-    } catch (...) {
-        return NFCS_ENOMEM;
-    }
-    a->committed = true;
-    return NFCS_OK;
-}
+NFCS_API int nfcs_acl_commit(nfcs_acl* a) { return table_commit(a, nfcs::acl_compile); }
 
 NFCS_API int nfcs_acl_upload(nfcs_ctx* c, nfcs_acl* a) {
     if (!c || !a || !a->committed) return NFCS_EINVAL;
-    acl_drop_upload(a);
-    DeviceGuard dg_(c->di.device);
-    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
     const nfcs::AclTables& t = a->t;
-    // one blob: the records (64 bytes each), then the actions
-    const size_t o_act = t.rec.size() * sizeof(nfcs::AclRec), total = o_act + t.act.size() * sizeof(nfcs::AclAct);
-    std::vector<uint8_t> blob(total + 16u, 0);
-    if (!t.rec.empty()) memcpy(blob.data(), t.rec.data(), o_act);
-    if (!t.act.empty()) memcpy(blob.data() + o_act, t.act.data(), total - o_act);
-    NFCS_HIP(hipMalloc(&a->d_blob, blob.size()));
-    a->device = c->di.device;
-    const hipError_t e = hipMemcpy(a->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        acl_drop_upload(a);
-        return hip_fail(e);
-    }
-    a->dev.rec = (const uint4*)a->d_blob;
-    a->dev.act = (const uint2*)(a->d_blob + o_act);
-    a->dev.rules = t.rules;
-    a->dev.rules_padded = (uint32_t)t.rec.size();
-    a->uploaded = true;
-    return NFCS_OK;
+    BlobLayout lay;
+    const size_t o_rec = lay.part(t.rec), o_act = lay.part(t.act);  // the records are 64 bytes each
+    return table_upload(c, a, lay, [&](const uint8_t* d) {
+        a->dev.rec = (const uint4*)(d + o_rec);
+        a->dev.act = (const uint2*)(d + o_act);
+        a->dev.rules = t.rules;
+        a->dev.rules_padded = (uint32_t)t.rec.size();
+    });
 }
 
 NFCS_API int nfcs_acl_eval_host(const nfcs_acl* a, const uint8_t* frame, uint32_t len, uint32_t* action,
@@ -1367,7 +1383,7 @@ NFCS_API int nfcs_acl_eval_host(const nfcs_acl* a, const uint8_t* frame, uint32_
 NFCS_API int nfcs_acl_eval_device(nfcs_ctx* c, const nfcs_acl* a, const uint8_t* d_arena, uint64_t arena_bytes,
                                   const nfcs_desc* d_desc, uint32_t n, uint8_t* d_action, uint32_t* d_rule,
                                   uint32_t* d_redirect, uint32_t* d_nh, void* stream) {
-    if (!c || !a || !a->uploaded || a->device != c->di.device) return NFCS_EINVAL;
+    if (!usable(c, a)) return NFCS_EINVAL;
     DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
     if (dg_.err != hipSuccess) return hip_fail(dg_.err);
     if (n == 0) return NFCS_OK;
@@ -1381,53 +1397,16 @@ NFCS_API int nfcs_acl_eval_device(nfcs_ctx* c, const nfcs_acl* a, const uint8_t*
 // ---- L2 forwarding database (nfcs_fdb.h: compile, host decision) and its lookup kernel -----------
 }  // extern "C"
 
-struct nfcs_fdb {
-    nfcs::FdbInputs in;
-    nfcs::FdbTables t;
-    bool committed = false;
-    // nfcs_fdb_upload: one device allocation holding every array, on `device`
-    int device = -1;
-    uint8_t* d_blob = nullptr;
-    nfcs::FdbDev dev;
-    bool uploaded = false;
-};
-
-namespace {
-void fdb_drop_upload(nfcs_fdb* f) {
-    if (f->d_blob) {
-        DeviceGuard dg_(f->device);
-        if (dg_.err == hipSuccess) (void)hipFree(f->d_blob);
-    }
-    f->d_blob = nullptr;
-    f->dev = nfcs::FdbDev{};
-    f->uploaded = false;
-}
-}  // namespace
+struct nfcs_fdb : Table<nfcs::FdbInputs, nfcs::FdbTables, nfcs::FdbDev> {};
 
 extern "C" {
 
-NFCS_API int nfcs_fdb_create(nfcs_fdb** out) {
-    if (!out) return NFCS_EINVAL;
-    *out = new (std::nothrow) nfcs_fdb();
-    return *out ? NFCS_OK : NFCS_ENOMEM;
-}
-
-NFCS_API int nfcs_fdb_destroy(nfcs_fdb* f) {
-    if (!f) return NFCS_EINVAL;
-    fdb_drop_upload(f);
-    delete f;
-    return NFCS_OK;
-}
+NFCS_API int nfcs_fdb_create(nfcs_fdb** out) { return table_create(out); }
+NFCS_API int nfcs_fdb_destroy(nfcs_fdb* f) { return table_destroy(f); }
 
 NFCS_API int nfcs_fdb_set_entries(nfcs_fdb* f, const nfcs_fdb_entry* entries, uint32_t n) {
-    if (!f || (n > 0 && !entries) || n > NFCS_FDB_MAX_ENTRIES) return NFCS_EINVAL;
-    try {
-        f->in.entries.assign(entries, entries + n);
-    } catch (...) {
-        return NFCS_ENOMEM;
-    }
-    f->committed = false;  // the device copy, if any, stays as it is until the next upload
-    return NFCS_OK;
+    if (n > NFCS_FDB_MAX_ENTRIES) return NFCS_EINVAL;
+    return table_assign(f, &nfcs::FdbInputs::entries, entries, n);
 }
 
 NFCS_API int nfcs_fdb_set_port(nfcs_fdb* f, const nfcs_l2_port* port, const uint16_t* allowed_vlans,
@@ -1436,74 +1415,38 @@ NFCS_API int nfcs_fdb_set_port(nfcs_fdb* f, const nfcs_l2_port* port, const uint
     if (port->port_id >= NFCS_L2_MAX_PORTS || port->native_vlan > 4095u || port->type > 2u) return NFCS_EINVAL;
     for (uint32_t i = 0; i < n_allowed; ++i)
         if (allowed_vlans[i] > 4095u) return NFCS_EINVAL;
-    try {
+    return table_set(f, [&] {
         if (f->in.ports.size() <= port->port_id) f->in.ports.resize(port->port_id + 1u);
         nfcs::FdbPortIn& pi = f->in.ports[port->port_id];
         pi.allowed.assign(allowed_vlans, allowed_vlans + n_allowed);
         pi.port = *port;
         pi.set = true;
-    } catch (...) {
-        return NFCS_ENOMEM;
-    }
-    f->committed = false;
-    return NFCS_OK;
+    });
 }
 
 NFCS_API int nfcs_fdb_clear_ports(nfcs_fdb* f) {
-    if (!f) return NFCS_EINVAL;
-    f->in.ports.clear();
-    f->committed = false;
-    return NFCS_OK;
+    return table_set(f, [&] { f->in.ports.clear(); });
 }
 
-NFCS_API int nfcs_fdb_commit(nfcs_fdb* f) {
-    if (!f) return NFCS_EINVAL;
-    try {
-        nfcs::fdb_compile(f->in, f->t);
-    } catch (...) {
-        return NFCS_ENOMEM;
-    }
-    f->committed = true;
-    return NFCS_OK;
-}
+NFCS_API int nfcs_fdb_commit(nfcs_fdb* f) { return table_commit(f, nfcs::fdb_compile); }
 
 NFCS_API int nfcs_fdb_upload(nfcs_ctx* c, nfcs_fdb* f) {
     if (!c || !f || !f->committed) return NFCS_EINVAL;
-    fdb_drop_upload(f);
-    DeviceGuard dg_(c->di.device);
-    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
     const nfcs::FdbTables& t = f->t;
-    // one blob, every array on a 16-byte boundary: the slots first (hipMalloc aligns them)
-    auto up16 = [](size_t x) { return (x + 15u) & ~size_t(15); };
-    const size_t b_slots = t.slots.size() * sizeof(nfcs::FdbSlot), b_vlans = t.port_vlans.size() * 4u;
-    const size_t o_vlans = b_slots, o_native = o_vlans + up16(b_vlans), o_state = o_native + up16(t.ports * 2u);
-    const size_t b_rows = t.vlan_ports.size() * 4u, o_rows = o_state + up16(t.ports);
-    const size_t total = o_rows + up16(b_rows) + 16u;
-    NFCS_HIP(hipMalloc(&f->d_blob, total));
-    f->device = c->di.device;
-    hipError_t e = hipMemset(f->d_blob, 0, total);
-    if (e == hipSuccess) e = hipMemcpy(f->d_blob, t.slots.data(), b_slots, hipMemcpyHostToDevice);
-    if (e == hipSuccess && t.ports) {
-        e = hipMemcpy(f->d_blob + o_vlans, t.port_vlans.data(), b_vlans, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(f->d_blob + o_native, t.port_native.data(), t.ports * 2u, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(f->d_blob + o_state, t.port_state.data(), t.ports, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(f->d_blob + o_rows, t.vlan_ports.data(), b_rows, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-        fdb_drop_upload(f);
-        return hip_fail(e);
-    }
-    f->dev.slots = (const uint4*)f->d_blob;
-    f->dev.slot_mask = (uint32_t)t.slots.size() - 1u;
-    f->dev.max_probe = t.max_probe;
-    f->dev.port_vlans = (const uint32_t*)(f->d_blob + o_vlans);
-    f->dev.port_native = (const uint16_t*)(f->d_blob + o_native);
-    f->dev.port_state = f->d_blob + o_state;
-    f->dev.ports = t.ports;
-    f->dev.vlan_ports = (const uint32_t*)(f->d_blob + o_rows);
-    f->dev.port_words = t.port_words;
-    f->uploaded = true;
-    return NFCS_OK;
+    BlobLayout lay;  // the slots (up to tens of MiB) are copied from where they are, like every part
+    const size_t o_slots = lay.part(t.slots), o_vlans = lay.part(t.port_vlans), o_native = lay.part(t.port_native);
+    const size_t o_state = lay.part(t.port_state), o_rows = lay.part(t.vlan_ports);
+    return table_upload(c, f, lay, [&](const uint8_t* d) {
+        f->dev.slots = (const uint4*)(d + o_slots);
+        f->dev.slot_mask = (uint32_t)t.slots.size() - 1u;
+        f->dev.max_probe = t.max_probe;
+        f->dev.port_vlans = (const uint32_t*)(d + o_vlans);
+        f->dev.port_native = (const uint16_t*)(d + o_native);
+        f->dev.port_state = d + o_state;
+        f->dev.ports = t.ports;
+        f->dev.vlan_ports = (const uint32_t*)(d + o_rows);
+        f->dev.port_words = t.port_words;
+    });
 }
 
 NFCS_API int nfcs_fdb_stats(const nfcs_fdb* f, uint32_t* entries, uint32_t* slots, uint32_t* max_probe,
@@ -1534,7 +1477,7 @@ NFCS_API int nfcs_l2_lookup_device(nfcs_ctx* c, const nfcs_fdb* f, uint32_t ingr
                                    uint64_t arena_bytes, const nfcs_desc* d_desc, uint32_t n,
                                    const uint8_t* d_rt_verdict, uint32_t* d_egress_port, uint8_t* d_verdict,
                                    uint16_t* d_vlan, uint8_t* d_learn, void* stream) {
-    if (!c || !f || !f->uploaded || f->device != c->di.device) return NFCS_EINVAL;
+    if (!usable(c, f)) return NFCS_EINVAL;
     DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
     if (dg_.err != hipSuccess) return hip_fail(dg_.err);
     if (n == 0) return NFCS_OK;
@@ -1571,7 +1514,7 @@ NFCS_API int nfcs_flood_expand_device(nfcs_ctx* c, const nfcs_fdb* f, uint32_t i
                                       const uint8_t* d_l2_verdict, const uint16_t* d_l2_vlan, uint32_t cap,
                                       nfcs_desc* d_item_desc, uint32_t* d_item_port, uint32_t* d_item_src,
                                       nfcs_flood_totals* d_totals, void* stream) {
-    if (!c || !f || !f->uploaded || f->device != c->di.device) return NFCS_EINVAL;
+    if (!usable(c, f)) return NFCS_EINVAL;
     if (!nfcs::flood_args_ok(num_ports, arena_bytes, copy_base, copy_align, n, d_l3_port, d_fwd_status, d_l2_port,
                              d_l2_verdict, d_l2_vlan))
         return NFCS_EINVAL;
@@ -1584,55 +1527,20 @@ NFCS_API int nfcs_flood_expand_device(nfcs_ctx* c, const nfcs_fdb* f, uint32_t i
         ((uintptr_t)d_item_desc & 7u) || ((uintptr_t)d_item_port & 3u) || ((uintptr_t)d_item_src & 3u))
         return NFCS_EINVAL;
     hipStream_t st = pick(c, stream);
-    hipError_t e = acquire_eq(c, nfcs::flood_scratch_words(n), st);  // the enqueue's scratch serves both
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();  // the context stays usable: only this call's scratch is missing
-        return NFCS_ENOMEM;
-    }
-    NFCS_HIP(e);
     const nfcs::FloodArgs a{d_arena, arena_bytes, copy_base, copy_align, ingress_port, num_ports, n, cap, d_desc,
                             d_l3_port, d_fwd_status, d_l2_port, d_l2_verdict, d_l2_vlan, d_item_desc, d_item_port,
                             d_item_src, d_totals};
-    NFCS_HIP(nfcs::launch_flood_expand(c->di, f->dev, a, c->eq_ws, st));
-    NFCS_HIP(release_eq(c, st));
-    return NFCS_OK;
+    return with_eq_scratch(c, nfcs::flood_scratch_words(n), st, [&](uint32_t* ws) {
+        return nfcs::launch_flood_expand(c->di, f->dev, a, ws, st);
+    });
 }
 
 // ---- ICMP responder (nfcs_icmp.h: compile, the plan, the host walk) and its kernels -----------------
 }  // extern "C"
 
-struct nfcs_icmp {
-    nfcs::IcmpInputs in;
-    nfcs::IcmpTables t;
-    bool committed = false;
-    // nfcs_icmp_upload: one device allocation holding every array, on `device`
-    int device = -1;
-    uint8_t* d_blob = nullptr;
-    nfcs::IcmpView dev{};
-    bool uploaded = false;
-};
+struct nfcs_icmp : Table<nfcs::IcmpInputs, nfcs::IcmpTables, nfcs::IcmpView> {};
 
 namespace {
-void icmp_drop_upload(nfcs_icmp* m) {
-    if (m->d_blob) {
-        DeviceGuard dg_(m->device);
-        if (dg_.err == hipSuccess) (void)hipFree(m->d_blob);
-    }
-    m->d_blob = nullptr;
-    m->dev = nfcs::IcmpView{};
-    m->uploaded = false;
-}
-template <class T>
-int icmp_set(nfcs_icmp* m, std::vector<T>& dst, const T* src, uint32_t n) {
-    if (!m || (n > 0 && !src)) return NFCS_EINVAL;
-    try {
-        dst.assign(src, src + n);
-    } catch (...) {
-        return NFCS_ENOMEM;
-    }
-    m->committed = false;  // the device copy, if any, stays as it is until the next upload
-    return NFCS_OK;
-}
 nfcs::FibView fib_dev_view(const nfcs_fib* f) {
     return nfcs::FibView{(const nfcs::U2*)f->dev.rt_nm, (const nfcs::U2*)f->dev.rt_info, f->dev.routes_padded,
                          f->dev.arp_ip, f->dev.arp_nh, f->dev.arps, f->d_table};
@@ -1641,76 +1549,35 @@ nfcs::FibView fib_dev_view(const nfcs_fib* f) {
 
 extern "C" {
 
-NFCS_API int nfcs_icmp_create(nfcs_icmp** out) {
-    if (!out) return NFCS_EINVAL;
-    *out = new (std::nothrow) nfcs_icmp();
-    return *out ? NFCS_OK : NFCS_ENOMEM;
-}
-
-NFCS_API int nfcs_icmp_destroy(nfcs_icmp* m) {
-    if (!m) return NFCS_EINVAL;
-    icmp_drop_upload(m);
-    delete m;
-    return NFCS_OK;
-}
+NFCS_API int nfcs_icmp_create(nfcs_icmp** out) { return table_create(out); }
+NFCS_API int nfcs_icmp_destroy(nfcs_icmp* m) { return table_destroy(m); }
 
 NFCS_API int nfcs_icmp_set_local(nfcs_icmp* m, const nfcs_icmp_local* local, uint32_t n) {
-    return m ? icmp_set(m, m->in.local, local, n) : NFCS_EINVAL;
+    return table_assign(m, &nfcs::IcmpInputs::local, local, n);
 }
 NFCS_API int nfcs_icmp_set_if_ips(nfcs_icmp* m, const nfcs_icmp_if_ip* if_ips, uint32_t n) {
-    return m ? icmp_set(m, m->in.if_ips, if_ips, n) : NFCS_EINVAL;
+    return table_assign(m, &nfcs::IcmpInputs::if_ips, if_ips, n);
 }
 NFCS_API int nfcs_icmp_set_ports_up(nfcs_icmp* m, const uint32_t* ports, uint32_t n, uint32_t num_ports) {
     if (!m || num_ports > nfcs::kIcmpMaxPorts) return NFCS_EINVAL;
-    const int rc = icmp_set(m, m->in.up, ports, n);
+    const int rc = table_assign(m, &nfcs::IcmpInputs::up, ports, n);
     if (rc == NFCS_OK) m->in.num_ports = num_ports;
     return rc;
 }
 
-NFCS_API int nfcs_icmp_commit(nfcs_icmp* m) {
-    if (!m) return NFCS_EINVAL;
-    try {
-        nfcs::icmp_compile(m->in, m->t);
-    } catch (...) {
-        return NFCS_ENOMEM;
-    }
-    m->committed = true;
-    return NFCS_OK;
-}
+NFCS_API int nfcs_icmp_commit(nfcs_icmp* m) { return table_commit(m, nfcs::icmp_compile); }
 
 NFCS_API int nfcs_icmp_upload(nfcs_ctx* c, nfcs_icmp* m) {
     if (!c || !m || !m->committed) return NFCS_EINVAL;
-    icmp_drop_upload(m);
-    DeviceGuard dg_(c->di.device);
-    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
     const nfcs::IcmpTables& t = m->t;
-    // one blob, every array on a 16-byte boundary
-    auto up16 = [](size_t x) { return (x + 15u) & ~size_t(15); };
-    const size_t o_lip = 0, o_lmac = o_lip + up16(t.local_ip.size() * 4u), o_iid = o_lmac + up16(t.local_mac.size() * 8u);
-    const size_t o_iip = o_iid + up16(t.if_id.size() * 4u), o_up = o_iip + up16(t.if_ip.size() * 4u);
-    const size_t total = o_up + up16(t.up.size() * 4u);
-    std::vector<uint8_t> blob(total + 16u, 0);
-    auto put = [&](size_t o, const void* p, size_t bytes) {
-        if (bytes) memcpy(blob.data() + o, p, bytes);
-    };
-    put(o_lip, t.local_ip.data(), t.local_ip.size() * 4u);
-    put(o_lmac, t.local_mac.data(), t.local_mac.size() * 8u);
-    put(o_iid, t.if_id.data(), t.if_id.size() * 4u);
-    put(o_iip, t.if_ip.data(), t.if_ip.size() * 4u);
-    put(o_up, t.up.data(), t.up.size() * 4u);
-    NFCS_HIP(hipMalloc(&m->d_blob, blob.size()));
-    m->device = c->di.device;
-    const hipError_t e = hipMemcpy(m->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        icmp_drop_upload(m);
-        return hip_fail(e);
-    }
-    m->dev = nfcs::IcmpView{(const uint32_t*)(m->d_blob + o_lip), (const nfcs::U2*)(m->d_blob + o_lmac),
-                            (uint32_t)t.local_ip.size(), (const uint32_t*)(m->d_blob + o_iid),
-                            (const uint32_t*)(m->d_blob + o_iip), (uint32_t)t.if_id.size(),
-                            (const uint32_t*)(m->d_blob + o_up), t.num_ports};
-    m->uploaded = true;
-    return NFCS_OK;
+    BlobLayout lay;
+    const size_t o_lip = lay.part(t.local_ip), o_lmac = lay.part(t.local_mac), o_iid = lay.part(t.if_id);
+    const size_t o_iip = lay.part(t.if_ip), o_up = lay.part(t.up);
+    return table_upload(c, m, lay, [&](const uint8_t* d) {
+        m->dev = nfcs::IcmpView{(const uint32_t*)(d + o_lip), (const nfcs::U2*)(d + o_lmac), (uint32_t)t.local_ip.size(),
+                                (const uint32_t*)(d + o_iid), (const uint32_t*)(d + o_iip), (uint32_t)t.if_id.size(),
+                                (const uint32_t*)(d + o_up), t.num_ports};
+    });
 }
 
 NFCS_API int nfcs_fib_resolve_host(const nfcs_fib* f, uint32_t ip, uint32_t* verdict, uint32_t* nh, uint32_t* egress_if) {
@@ -1746,8 +1613,8 @@ NFCS_API int nfcs_icmp_respond_device(nfcs_ctx* c, const nfcs_icmp* m, const nfc
                                       const nfcs_desc* d_desc, uint32_t n, const uint8_t* d_rt_verdict,
                                       const uint16_t* d_ip_id, uint32_t cap, nfcs_desc* d_msg_desc, uint32_t* d_msg_port,
                                       uint32_t* d_msg_src, uint8_t* d_status, nfcs_icmp_totals* d_totals, void* stream) {
-    if (!c || !m || !m->uploaded || m->device != c->di.device) return NFCS_EINVAL;
-    if (!f || !f->uploaded || f->device != c->di.device) return NFCS_EINVAL;
+    if (!usable(c, m)) return NFCS_EINVAL;
+    if (!usable(c, f)) return NFCS_EINVAL;
     if (!nfcs::icmp_args_ok(arena_bytes, msg_base, msg_align)) return NFCS_EINVAL;
     DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
     if (dg_.err != hipSuccess) return hip_fail(dg_.err);
@@ -1759,113 +1626,50 @@ NFCS_API int nfcs_icmp_respond_device(nfcs_ctx* c, const nfcs_icmp* m, const nfc
         ((uintptr_t)d_msg_src & 3u))
         return NFCS_EINVAL;
     hipStream_t st = pick(c, stream);
-    hipError_t e = acquire_eq(c, nfcs::flood_scratch_words(n), st);  // the enqueue's scratch serves this stage too
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();  // the context stays usable: only this call's scratch is missing
-        return NFCS_ENOMEM;
-    }
-    NFCS_HIP(e);
     const nfcs::IcmpArgs a{d_arena, arena_bytes, msg_base, msg_align, ingress_port, n, cap, d_desc, d_rt_verdict, d_ip_id,
                            d_msg_desc, d_msg_port, d_msg_src, d_status, d_totals};
-    NFCS_HIP(nfcs::launch_icmp_respond(c->di, m->dev, fib_dev_view(f), a, c->eq_ws, st));
-    NFCS_HIP(release_eq(c, st));
-    return NFCS_OK;
+    return with_eq_scratch(c, nfcs::flood_scratch_words(n), st, [&](uint32_t* ws) {
+        return nfcs::launch_icmp_respond(c->di, m->dev, fib_dev_view(f), a, ws, st);
+    });
 }
 
 // ---- Egress stage (nfcs_egress.h: compile, host plan, host enqueue) and its kernels ----------------
 }  // extern "C"
 
-struct nfcs_egress {
-    nfcs::EgressInputs in;
-    nfcs::EgressTables t;
-    bool committed = false;
-    // nfcs_egress_upload: the records on `device`
-    int device = -1;
-    uint8_t* d_blob = nullptr;
-    nfcs::EgressDev dev;
-    bool uploaded = false;
-};
-
-namespace {
-void egress_drop_upload(nfcs_egress* g) {
-    if (g->d_blob) {
-        DeviceGuard dg_(g->device);
-        if (dg_.err == hipSuccess) (void)hipFree(g->d_blob);
-    }
-    g->d_blob = nullptr;
-    g->dev = nfcs::EgressDev{};
-    g->uploaded = false;
-}
-}  // namespace
+struct nfcs_egress : Table<nfcs::EgressInputs, nfcs::EgressTables, nfcs::EgressDev> {};
 
 extern "C" {
 
-NFCS_API int nfcs_egress_create(nfcs_egress** out) {
-    if (!out) return NFCS_EINVAL;
-    *out = new (std::nothrow) nfcs_egress();
-    return *out ? NFCS_OK : NFCS_ENOMEM;
-}
-
-NFCS_API int nfcs_egress_destroy(nfcs_egress* g) {
-    if (!g) return NFCS_EINVAL;
-    egress_drop_upload(g);
-    delete g;
-    return NFCS_OK;
-}
+NFCS_API int nfcs_egress_create(nfcs_egress** out) { return table_create(out); }
+NFCS_API int nfcs_egress_destroy(nfcs_egress* g) { return table_destroy(g); }
 
 NFCS_API int nfcs_egress_set_port(nfcs_egress* g, const nfcs_egress_port* port) {
     if (!g || !port) return NFCS_EINVAL;
     if (port->port_id >= NFCS_L2_MAX_PORTS || port->type > 2u || port->native_vlan > 4095u ||
         port->num_queues > NFCS_QOS_MAX_QUEUES)
         return NFCS_EINVAL;
-    try {
+    return table_set(g, [&] {
         if (g->in.ports.size() <= port->port_id) g->in.ports.resize(port->port_id + 1u);
         g->in.ports[port->port_id].port = *port;
         g->in.ports[port->port_id].set = true;
-    } catch (...) {
-        return NFCS_ENOMEM;
-    }
-    g->committed = false;  // the device copy, if any, stays as it is until the next upload
-    return NFCS_OK;
+    });
 }
 
 NFCS_API int nfcs_egress_clear_ports(nfcs_egress* g) {
-    if (!g) return NFCS_EINVAL;
-    g->in.ports.clear();
-    g->committed = false;
-    return NFCS_OK;
+    return table_set(g, [&] { g->in.ports.clear(); });
 }
 
-NFCS_API int nfcs_egress_commit(nfcs_egress* g) {
-    if (!g) return NFCS_EINVAL;
-    try {
-        nfcs::egress_compile(g->in, g->t);
-    } catch (...) {
-        return NFCS_ENOMEM;
-    }
-    g->committed = true;
-    return NFCS_OK;
-}
+NFCS_API int nfcs_egress_commit(nfcs_egress* g) { return table_commit(g, nfcs::egress_compile); }
 
 NFCS_API int nfcs_egress_upload(nfcs_ctx* c, nfcs_egress* g) {
     if (!c || !g || !g->committed) return NFCS_EINVAL;
-    egress_drop_upload(g);
-    DeviceGuard dg_(c->di.device);
-    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
-    const size_t bytes = g->t.recs.size() * sizeof(nfcs::EgressRec);
-    NFCS_HIP(hipMalloc(&g->d_blob, bytes + 16u));
-    g->device = c->di.device;
-    hipError_t e = hipMemset(g->d_blob, 0, bytes + 16u);
-    if (e == hipSuccess && bytes) e = hipMemcpy(g->d_blob, g->t.recs.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        egress_drop_upload(g);
-        return hip_fail(e);
-    }
-    g->dev.recs = (const uint4*)g->d_blob;
-    g->dev.ports = g->t.ports;
-    g->dev.keys = g->t.keys;
-    g->uploaded = true;
-    return NFCS_OK;
+    BlobLayout lay;
+    const size_t o_recs = lay.part(g->t.recs);
+    return table_upload(c, g, lay, [&](const uint8_t* d) {
+        g->dev.recs = (const uint4*)(d + o_recs);
+        g->dev.ports = g->t.ports;
+        g->dev.keys = g->t.keys;
+    });
 }
 
 NFCS_API int nfcs_egress_keys(const nfcs_egress* g, uint32_t* ports, uint32_t* keys) {
@@ -1899,7 +1703,7 @@ NFCS_API int nfcs_egress_plan_device(nfcs_ctx* c, const nfcs_egress* g, const ui
                                      const nfcs_desc* d_desc, uint32_t n, const uint32_t* d_l3_port,
                                      const uint8_t* d_fwd_status, const uint32_t* d_l2_port, uint32_t* d_port,
                                      uint32_t* d_ops, uint8_t* d_queue, void* stream) {
-    if (!c || !g || !g->uploaded || g->device != c->di.device) return NFCS_EINVAL;
+    if (!usable(c, g)) return NFCS_EINVAL;
     if ((!d_l3_port && !d_l2_port) || (d_fwd_status && !d_l3_port)) return NFCS_EINVAL;
     DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
     if (dg_.err != hipSuccess) return hip_fail(dg_.err);
@@ -1915,7 +1719,7 @@ NFCS_API int nfcs_egress_plan_device(nfcs_ctx* c, const nfcs_egress* g, const ui
 NFCS_API int nfcs_egress_enqueue_device(nfcs_ctx* c, const nfcs_egress* g, const uint32_t* d_port, const uint8_t* d_queue,
                                         uint32_t n, uint32_t* d_depth, uint8_t* d_result, uint32_t* d_order,
                                         uint32_t* d_key_start, uint32_t* d_key_dropped, void* stream) {
-    if (!c || !g || !g->uploaded || g->device != c->di.device) return NFCS_EINVAL;
+    if (!usable(c, g)) return NFCS_EINVAL;
     DeviceGuard dg_(c->di.device);
     if (dg_.err != hipSuccess) return hip_fail(dg_.err);
     if (n == 0) return NFCS_OK;
@@ -1924,140 +1728,49 @@ NFCS_API int nfcs_egress_enqueue_device(nfcs_ctx* c, const nfcs_egress* g, const
         ((uintptr_t)d_key_start & 3u) || ((uintptr_t)d_key_dropped & 3u))
         return NFCS_EINVAL;
     hipStream_t st = pick(c, stream);
-    const uint64_t words = nfcs::egress_scratch_words(n, g->dev.keys);
-    hipError_t e = acquire_eq(c, words, st);
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();  // the context stays usable: only this call's scratch is missing
-        return NFCS_ENOMEM;
-    }
-    NFCS_HIP(e);
-    NFCS_HIP(nfcs::launch_egress_enqueue(c->di, g->dev, d_port, d_queue, n, d_depth, d_result, d_order, d_key_start,
-                                         d_key_dropped, c->eq_ws, st));
-    NFCS_HIP(release_eq(c, st));
-    return NFCS_OK;
+    return with_eq_scratch(c, nfcs::egress_scratch_words(n, g->dev.keys), st, [&](uint32_t* ws) {
+        return nfcs::launch_egress_enqueue(c->di, g->dev, d_port, d_queue, n, d_depth, d_result, d_order, d_key_start,
+                                           d_key_dropped, ws, st);
+    });
 }
 
 // ---- Egress ACLs (nfcs_aclset.h: lists, bindings, compile, host decision) and their kernel ---------
 }  // extern "C"
 
-struct nfcs_aclset {
-    nfcs::AclSetInputs in;
-    nfcs::AclSetTables t;
-    bool committed = false;
-    // nfcs_aclset_upload: one device allocation holding the three arrays, on `device`
-    int device = -1;
-    uint8_t* d_blob = nullptr;
-    nfcs::AclSetDev dev;
-    bool uploaded = false;
-};
-
-namespace {
-void aclset_drop_upload(nfcs_aclset* s) {
-    if (s->d_blob) {
-        DeviceGuard dg_(s->device);
-        if (dg_.err == hipSuccess) (void)hipFree(s->d_blob);
-    }
-    s->d_blob = nullptr;
-    s->dev = nfcs::AclSetDev{};
-    s->uploaded = false;
-}
-}  // namespace
+struct nfcs_aclset : Table<nfcs::AclSetInputs, nfcs::AclSetTables, nfcs::AclSetDev> {};
 
 extern "C" {
 
-NFCS_API int nfcs_aclset_create(nfcs_aclset** out) {
-    if (!out) return NFCS_EINVAL;
-    *out = new (std::nothrow) nfcs_aclset();
-    return *out ? NFCS_OK : NFCS_ENOMEM;
-}
+NFCS_API int nfcs_aclset_create(nfcs_aclset** out) { return table_create(out); }
+NFCS_API int nfcs_aclset_destroy(nfcs_aclset* s) { return table_destroy(s); }
 
-NFCS_API int nfcs_aclset_destroy(nfcs_aclset* s) {
-    if (!s) return NFCS_EINVAL;
-    aclset_drop_upload(s);
-    delete s;
-    return NFCS_OK;
-}
-
-// every setter: the device copy, if any, stays as it is until the next upload
 NFCS_API int nfcs_aclset_set_list(nfcs_aclset* s, uint32_t list_id, const nfcs_acl_rule* rules, uint32_t n) {
-    if (!s) return NFCS_EINVAL;
-    try {
-        const int rc = nfcs::aclset_set_list(s->in, list_id, rules, n);
-        if (rc != NFCS_OK) return rc;
-    } catch (...) {
-        return NFCS_ENOMEM;
-    }
-    s->committed = false;
-    return NFCS_OK;
+    return table_set(s, [&] { return nfcs::aclset_set_list(s->in, list_id, rules, n); });
 }
-
 NFCS_API int nfcs_aclset_remove_list(nfcs_aclset* s, uint32_t list_id) {
-    if (!s) return NFCS_EINVAL;
-    const int rc = nfcs::aclset_remove_list(s->in, list_id);
-    if (rc != NFCS_OK) return rc;
-    s->committed = false;
-    return NFCS_OK;
+    return table_set(s, [&] { return nfcs::aclset_remove_list(s->in, list_id); });
 }
-
 NFCS_API int nfcs_aclset_bind_port(nfcs_aclset* s, uint32_t port_id, uint32_t list_id) {
-    if (!s) return NFCS_EINVAL;
-    try {
-        const int rc = nfcs::aclset_bind_port(s->in, port_id, list_id);
-        if (rc != NFCS_OK) return rc;
-    } catch (...) {
-        return NFCS_ENOMEM;
-    }
-    s->committed = false;
-    return NFCS_OK;
+    return table_set(s, [&] { return nfcs::aclset_bind_port(s->in, port_id, list_id); });
 }
-
 NFCS_API int nfcs_aclset_clear(nfcs_aclset* s) {
-    if (!s) return NFCS_EINVAL;
-    nfcs::aclset_clear(s->in);
-    s->committed = false;
-    return NFCS_OK;
+    return table_set(s, [&] { nfcs::aclset_clear(s->in); });
 }
 
-NFCS_API int nfcs_aclset_commit(nfcs_aclset* s) {
-    if (!s) return NFCS_EINVAL;
-    s->committed = false;
-    try {
-        const int rc = nfcs::aclset_compile(s->in, s->t);
-        if (rc != NFCS_OK) return rc;
-    } catch (...) {
-        return NFCS_ENOMEM;
-    }
-    s->committed = true;
-    return NFCS_OK;
-}
+NFCS_API int nfcs_aclset_commit(nfcs_aclset* s) { return table_commit(s, nfcs::aclset_compile); }
 
 NFCS_API int nfcs_aclset_upload(nfcs_ctx* c, nfcs_aclset* s) {
     if (!c || !s || !s->committed) return NFCS_EINVAL;
-    aclset_drop_upload(s);
-    DeviceGuard dg_(c->di.device);
-    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
     const nfcs::AclSetTables& t = s->t;
-    // one blob: the records (64 bytes each), then the actions, then the ports' bindings (8 bytes each)
-    const size_t o_act = t.rec.size() * sizeof(nfcs::AclRec), o_bind = o_act + t.act.size() * sizeof(nfcs::AclAct),
-                 total = o_bind + t.bind.size() * sizeof(nfcs::AclBind);
-    std::vector<uint8_t> blob(total + 16u, 0);
-    if (!t.rec.empty()) memcpy(blob.data(), t.rec.data(), o_act);
-    if (!t.act.empty()) memcpy(blob.data() + o_act, t.act.data(), o_bind - o_act);
-    if (!t.bind.empty()) memcpy(blob.data() + o_bind, t.bind.data(), total - o_bind);
-    NFCS_HIP(hipMalloc(&s->d_blob, blob.size()));
-    s->device = c->di.device;
-    const hipError_t e = hipMemcpy(s->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        aclset_drop_upload(s);
-        return hip_fail(e);
-    }
-    s->dev.rec = (const uint4*)s->d_blob;
-    s->dev.act = (const uint2*)(s->d_blob + o_act);
-    s->dev.bind = (const uint2*)(s->d_blob + o_bind);
-    s->dev.ports = t.ports;
-    s->dev.rules_padded = (uint32_t)t.rec.size();
-    s->uploaded = true;
-    return NFCS_OK;
+    BlobLayout lay;  // the records (64 bytes each), the actions, the ports' bindings (8 bytes each)
+    const size_t o_rec = lay.part(t.rec), o_act = lay.part(t.act), o_bind = lay.part(t.bind);
+    return table_upload(c, s, lay, [&](const uint8_t* d) {
+        s->dev.rec = (const uint4*)(d + o_rec);
+        s->dev.act = (const uint2*)(d + o_act);
+        s->dev.bind = (const uint2*)(d + o_bind);
+        s->dev.ports = t.ports;
+        s->dev.rules_padded = (uint32_t)t.rec.size();
+    });
 }
 
 NFCS_API int nfcs_aclset_info(const nfcs_aclset* s, uint32_t* ports, uint32_t* lists, uint32_t* rules_padded) {
@@ -2089,7 +1802,7 @@ NFCS_API int nfcs_egress_acl_device(nfcs_ctx* c, const nfcs_aclset* s, const uin
                                     const nfcs_desc* d_desc, uint32_t n, uint32_t* d_port, uint8_t* d_action,
                                     uint32_t* d_rule, uint32_t* d_redirect, uint32_t* d_denied_pkts,
                                     uint64_t* d_denied_bytes, void* stream) {
-    if (!c || !s || !s->uploaded || s->device != c->di.device) return NFCS_EINVAL;
+    if (!usable(c, s)) return NFCS_EINVAL;
     if (!d_denied_pkts != !d_denied_bytes) return NFCS_EINVAL;
     DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
     if (dg_.err != hipSuccess) return hip_fail(dg_.err);
@@ -2136,33 +1849,22 @@ void txq_free_device(nfcs_txq* x) {
 // tables; heads, last and scratch start as zero.
 int txq_make_device(nfcs_ctx* c, nfcs_txq* x) {
     const nfcs::TxqTables& t = x->t;
-    size_t off = 0;
-    auto part = [&off](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 15u) & ~(size_t)15u;
-        return at;
-    };
-    const size_t o_port = part((size_t)t.ports * sizeof(nfcs::TxqPort));
-    const size_t o_base = part(((size_t)t.keys + 1u) * sizeof(uint64_t));
-    const size_t o_head = part((size_t)t.keys * 4u);
-    const size_t o_last = part((size_t)t.ports * 4u);
-    const size_t o_take = part((size_t)t.keys * 4u);
-    const size_t o_elem = part(((size_t)t.keys + 1u) * 4u);
-    const size_t o_txs = part(((size_t)t.ports + 1u) * 4u);
-    const size_t o_nl = part((size_t)t.ports * 4u);
+    BlobLayout lay;
+    const size_t o_port = lay.part(t.port);
+    const size_t o_base = lay.part(t.ring_base);
+    const size_t o_head = lay.part(nullptr, (size_t)t.keys * 4u);
+    const size_t o_last = lay.part(nullptr, (size_t)t.ports * 4u);
+    const size_t o_take = lay.part(nullptr, (size_t)t.keys * 4u);
+    const size_t o_elem = lay.part(nullptr, ((size_t)t.keys + 1u) * 4u);
+    const size_t o_txs = lay.part(nullptr, ((size_t)t.ports + 1u) * 4u);
+    const size_t o_nl = lay.part(nullptr, (size_t)t.ports * 4u);
     if (t.ring_slots > (SIZE_MAX >> 4)) return NFCS_ENOMEM;
     DeviceGuard dg_(c->di.device);
     if (dg_.err != hipSuccess) return hip_fail(dg_.err);
     x->device = c->di.device;
-    hipError_t e = hipMalloc(&x->d_blob, off + 16u);
+    hipError_t e = lay.upload(&x->d_blob);
     if (e == hipSuccess) e = hipMalloc(&x->d_ring, (size_t)t.ring_slots * 8u + 16u);
-    if (e == hipSuccess) e = hipMemset(x->d_blob, 0, off + 16u);
     if (e == hipSuccess) e = hipMemset(x->d_ring, 0, (size_t)t.ring_slots * 8u + 16u);
-    if (e == hipSuccess && t.ports)
-        e = hipMemcpy(x->d_blob + o_port, t.port.data(), (size_t)t.ports * sizeof(nfcs::TxqPort), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMemcpy(x->d_blob + o_base, t.ring_base.data(), ((size_t)t.keys + 1u) * sizeof(uint64_t),
-                      hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         txq_free_device(x);
