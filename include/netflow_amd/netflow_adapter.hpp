@@ -174,6 +174,30 @@ inline int l2_lookup_batch(const std::vector<netflow::Packet*>& pkts, const nfcs
     return l2_lookup_batch(pkts.data(), pkts.size(), fdb, ingress_port, egress_port, verdict, vlan, learn, rt_verdict);
 }
 
+// What process_received_packet does between the stages, for the burst the three lookups just decided
+// (ChecksumEngine::ingress_dispatch_batch, packet.hpp): the ingress link test, DENY / REDIRECT and the LLDP,
+// zero-MAC and ARP early returns masking next_hop, l2_port and l2_verdict, and the RX counters. As with the other
+// overloads over netflow::Packet*, the tested path is the same template over netflow_amd::Packet
+// (tests/cpp/dispatch_test.cpp).
+inline int ingress_dispatch_batch(netflow::Packet* const* pkts, size_t n, const nfcs_fdb* fdb, uint32_t ingress_port,
+                                  uint32_t num_ports, const uint8_t* rt_verdict, uint32_t* next_hop, uint32_t* l2_port,
+                                  uint8_t* l2_verdict, const uint8_t* action = nullptr,
+                                  const uint32_t* redirect_port = nullptr, uint8_t* cls = nullptr,
+                                  uint8_t* bypass = nullptr, nfcs_rx_stats* rx = nullptr) {
+    return detail::on_default_engine([&](ChecksumEngine& e) {
+        return e.ingress_dispatch_batch(pkts, n, fdb, ingress_port, num_ports, rt_verdict, next_hop, l2_port, l2_verdict,
+                                        action, redirect_port, cls, bypass, rx);
+    });
+}
+inline int ingress_dispatch_batch(const std::vector<netflow::Packet*>& pkts, const nfcs_fdb* fdb, uint32_t ingress_port,
+                                  uint32_t num_ports, const uint8_t* rt_verdict, uint32_t* next_hop, uint32_t* l2_port,
+                                  uint8_t* l2_verdict, const uint8_t* action = nullptr,
+                                  const uint32_t* redirect_port = nullptr, uint8_t* cls = nullptr,
+                                  uint8_t* bypass = nullptr, nfcs_rx_stats* rx = nullptr) {
+    return ingress_dispatch_batch(pkts.data(), pkts.size(), fdb, ingress_port, num_ports, rt_verdict, next_hop, l2_port,
+                                  l2_verdict, action, redirect_port, cls, bypass, rx);
+}
+
 // A committed forwarding database (nfcs_fdb) from the switch's own L2 state: ForwardingDatabase::
 // get_all_entries() as it is, and for the ports 0 .. num_ports - 1 VlanManager::get_port_config plus the
 // two predicates the L2 block asks per port — link_up(port) for InterfaceManager::is_port_link_up and

@@ -270,6 +270,21 @@ public:
     int l2_lookup_batch(Pkt* const* pkts, size_t n, const nfcs_fdb* fdb, uint32_t ingress_port,
                         uint32_t* egress_port, uint8_t* verdict = nullptr, uint16_t* vlan = nullptr,
                         uint8_t* learn = nullptr, const uint8_t* rt_verdict = nullptr);
+    // What Switch::process_received_packet does between the stages (switch.hpp:215-266; nfcs_ingress_dispatch_device)
+    // for a batch received on ingress_port of a switch with num_ports ports, after route_lookup_batch,
+    // acl_eval_batch and l2_lookup_batch on the same packets: rt_verdict is the route lookup's, action and
+    // redirect_port the ingress ACL's (both nullptr: the port has no ingress list), next_hop, l2_port and l2_verdict
+    // (in/out, all required) the three calls' outputs. A frame the switch drops, punts (LLDP, zero MAC, ARP) or
+    // redirects loses its next hop, port and flood; a valid REDIRECT gets its port in l2_port and bypass[i] = 1.
+    // cls[i] (optional) = NFCS_SW_*. rx (optional): the RX counters of ingress_port, added to. The staged copies
+    // are cut to 32 bytes, so the counters are summed here from the classes and the packets' own lengths by the
+    // rule of nfcs_ingress_dispatch_device (a dropped frame counts twice, as in the reference). Reads the first 32
+    // bytes of each packet at most; the packets are not changed.
+    template <class Pkt>
+    int ingress_dispatch_batch(Pkt* const* pkts, size_t n, const nfcs_fdb* fdb, uint32_t ingress_port, uint32_t num_ports,
+                               const uint8_t* rt_verdict, uint32_t* next_hop, uint32_t* l2_port, uint8_t* l2_verdict,
+                               const uint8_t* action = nullptr, const uint32_t* redirect_port = nullptr,
+                               uint8_t* cls = nullptr, uint8_t* bypass = nullptr, nfcs_rx_stats* rx = nullptr);
     // nfcs_fdb_upload to this engine's device, serialised with its other calls. The fdb must be
     // destroyed before the engine.
     int upload_fdb(nfcs_fdb* fdb) {
@@ -780,6 +795,69 @@ int ChecksumEngine::l2_lookup_batch(Pkt* const* pkts, size_t n, const nfcs_fdb* 
     if (verdict && (rc = nfcs_memcpy_d2h(ctx_, verdict, d_status_, n))) return rc;
     if (vlan && (rc = nfcs_memcpy_d2h(ctx_, vlan, dvlan.p, n * sizeof(uint16_t)))) return rc;
     if (learn && (rc = nfcs_memcpy_d2h(ctx_, learn, dlearn.p, n))) return rc;
+    return NFCS_OK;
+}
+
+template <class Pkt>
+int ChecksumEngine::ingress_dispatch_batch(Pkt* const* pkts, size_t n, const nfcs_fdb* fdb, uint32_t ingress_port,
+                                           uint32_t num_ports, const uint8_t* rt_verdict, uint32_t* next_hop,
+                                           uint32_t* l2_port, uint8_t* l2_verdict, const uint8_t* action,
+                                           const uint32_t* redirect_port, uint8_t* cls, uint8_t* bypass,
+                                           nfcs_rx_stats* rx) {
+    if (n == 0) return NFCS_OK;
+    if (!pkts || !fdb || !rt_verdict || !next_hop || !l2_port || !l2_verdict || n > 0xFFFFFFFFu) return NFCS_EINVAL;
+    std::lock_guard<std::mutex> lock(mu_);
+    // gather clamps each length to 32: the decision tests lengths against 14 and 18 only
+    int rc = reserve(n * 32 + 16, n);
+    if (rc) return rc;
+    const size_t off = gather(pkts, n, 32);
+    DevTmp dnh(ctx_, n * sizeof(uint32_t), rc);
+    DevTmp dport(ctx_, n * sizeof(uint32_t), rc);
+    DevTmp dred(ctx_, n * sizeof(uint32_t), rc);
+    DevTmp dl2v(ctx_, n, rc);
+    DevTmp drt(ctx_, n, rc);
+    DevTmp dact(ctx_, n, rc);
+    DevTmp dbyp(ctx_, n, rc);
+    if (rc) return rc;
+    const uint32_t m = static_cast<uint32_t>(n);
+    if ((rc = nfcs_memcpy_h2d(ctx_, d_arena_, h_arena_, off ? off : 16))) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, d_desc_, h_desc_, n * sizeof(nfcs_desc)))) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, drt.p, rt_verdict, n))) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, dnh.p, next_hop, n * sizeof(uint32_t)))) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, dport.p, l2_port, n * sizeof(uint32_t)))) return rc;
+    if ((rc = nfcs_memcpy_h2d(ctx_, dl2v.p, l2_verdict, n))) return rc;
+    if (action && (rc = nfcs_memcpy_h2d(ctx_, dact.p, action, n))) return rc;
+    if (redirect_port && (rc = nfcs_memcpy_h2d(ctx_, dred.p, redirect_port, n * sizeof(uint32_t)))) return rc;
+    if ((rc = nfcs_ingress_dispatch_device(ctx_, fdb, ingress_port, num_ports, static_cast<uint8_t*>(d_arena_),
+                                           off ? off : 16, static_cast<nfcs_desc*>(d_desc_), m,
+                                           action ? static_cast<uint8_t*>(dact.p) : nullptr,
+                                           redirect_port ? static_cast<uint32_t*>(dred.p) : nullptr,
+                                           static_cast<uint8_t*>(drt.p), static_cast<uint32_t*>(dnh.p),
+                                           static_cast<uint32_t*>(dport.p), static_cast<uint8_t*>(dl2v.p),
+                                           static_cast<uint8_t*>(d_status_), static_cast<uint8_t*>(dbyp.p), nullptr,
+                                           nullptr)))
+        return rc;
+    if ((rc = nfcs_memcpy_d2h(ctx_, next_hop, dnh.p, n * sizeof(uint32_t)))) return rc;
+    if ((rc = nfcs_memcpy_d2h(ctx_, l2_port, dport.p, n * sizeof(uint32_t)))) return rc;
+    if ((rc = nfcs_memcpy_d2h(ctx_, l2_verdict, dl2v.p, n))) return rc;
+    if (bypass && (rc = nfcs_memcpy_d2h(ctx_, bypass, dbyp.p, n))) return rc;
+    std::vector<uint8_t> own;
+    if (rx && !cls) {
+        own.resize(n);
+        cls = own.data();
+    }
+    if (cls && (rc = nfcs_memcpy_d2h(ctx_, cls, d_status_, n))) return rc;
+    if (rx) {
+        for (size_t i = 0; i < n; ++i) {
+            if (cls[i] == NFCS_SW_RX_DOWN) continue;  // switch.hpp:215 returns before 216
+            auto* b = pkts[i] ? pkts[i]->get_buffer() : nullptr;
+            const uint64_t len = b ? b->get_data_length() : 0;
+            const bool drop = cls[i] == NFCS_SW_IN_DENY || cls[i] == NFCS_SW_RED_DOWN || cls[i] == NFCS_SW_RED_RANGE;
+            rx->rx_packets += drop ? 2u : 1u;  // 216, and once more at 228 / 235
+            rx->rx_bytes += drop ? 2u * len : len;
+            rx->rx_drops += drop ? 1u : 0u;
+        }
+    }
     return NFCS_OK;
 }
 
@@ -1511,6 +1589,16 @@ inline int l2_lookup_batch(Packet* const* pkts, size_t n, const nfcs_fdb* fdb, u
                            uint8_t* learn = nullptr, const uint8_t* rt_verdict = nullptr) {
     return detail::on_default_engine([&](ChecksumEngine& e) {
         return e.l2_lookup_batch(pkts, n, fdb, ingress_port, egress_port, verdict, vlan, learn, rt_verdict);
+    });
+}
+inline int ingress_dispatch_batch(Packet* const* pkts, size_t n, const nfcs_fdb* fdb, uint32_t ingress_port,
+                                  uint32_t num_ports, const uint8_t* rt_verdict, uint32_t* next_hop, uint32_t* l2_port,
+                                  uint8_t* l2_verdict, const uint8_t* action = nullptr,
+                                  const uint32_t* redirect_port = nullptr, uint8_t* cls = nullptr,
+                                  uint8_t* bypass = nullptr, nfcs_rx_stats* rx = nullptr) {
+    return detail::on_default_engine([&](ChecksumEngine& e) {
+        return e.ingress_dispatch_batch(pkts, n, fdb, ingress_port, num_ports, rt_verdict, next_hop, l2_port, l2_verdict,
+                                        action, redirect_port, cls, bypass, rx);
     });
 }
 inline int flood_expand_batch(Packet* const* pkts, size_t n, const nfcs_fdb* fdb, uint32_t ingress_port,

@@ -696,7 +696,8 @@ NFCS_API int nfcs_l2_lookup_device(nfcs_ctx* ctx, const nfcs_fdb* fdb, uint32_t 
  *    usable, as the enqueue does.
  * Per-port egress ACLs on the copies: nfcs_egress_acl_device over the item list, between nfcs_vlan_device
  * and nfcs_egress_enqueue_device (the egress ACLs' section).
- * STILL OUT OF SCOPE: the ingress ACL's REDIRECT path; interface TX counters. */
+ * The ingress ACL's REDIRECT path: nfcs_ingress_dispatch_device (the ingress dispatch's section) puts a valid
+ * redirect's port into d_l2_port before this call. STILL OUT OF SCOPE: interface TX counters. */
 #define NFCS_FLOOD_TILE_PKTS 1024u /* packets per scan tile; SPEED ONLY, tests place sizes around it */
 #define NFCS_ITEM_NONE 0xFFFFFFFFu
 
@@ -1144,8 +1145,9 @@ NFCS_API int nfcs_aclset_eval_host(const nfcs_aclset* set, uint32_t port, const 
  * n == 0 returns NFCS_OK without a launch. set must be uploaded to ctx (else NFCS_EINVAL) and stay unchanged
  * until the call completes. A wave whose packets all leave by one port runs nfcs_acl_eval_device's scan;
  * a wave with several lists scans each of them once.
- * OUT OF SCOPE: the ingress ACL's REDIRECT path; choosing the INGRESS list per packet; interface RX / TX
- * counters other than the deny counters above. */
+ * The ingress ACL's REDIRECT path, whose items bypass this ACL, is nfcs_egress_acl_items_device, and the interface
+ * RX counters are nfcs_ingress_dispatch_device's (the ingress dispatch's section).
+ * OUT OF SCOPE: choosing the INGRESS list per packet; interface TX counters other than the deny counters above. */
 NFCS_API int nfcs_egress_acl_device(nfcs_ctx* ctx, const nfcs_aclset* set, const uint8_t* d_arena,
                                     uint64_t arena_bytes, const nfcs_desc* d_desc, uint32_t n, uint32_t* d_port,
                                     uint8_t* d_action, uint32_t* d_rule, uint32_t* d_redirect,
@@ -1248,6 +1250,169 @@ NFCS_API int nfcs_txq_dequeue_host(nfcs_txq* txq, const uint32_t* budget, uint32
 NFCS_API int nfcs_txq_closed_form_host(uint32_t sched, uint32_t num_queues, uint32_t last, const uint32_t* depth,
                                        uint32_t budget, uint32_t* take, uint32_t* new_last, uint8_t* seq,
                                        uint32_t seq_cap);
+
+/* ---- Ingress dispatch and the one-call RX pipeline --------------------------------------------- */
+
+/* The lines of Switch::process_received_packet (switch.hpp:213-329) that belong to no manager, for one RX
+ * burst of one ingress port: the ingress link test (215), the RX counters (216, 228, 235), DENY and REDIRECT
+ * overriding the L3 and L2 decisions (226-243), REDIRECT's port test (233) and its bypass of the egress ACL
+ * (238-240), and the LLDP, zero-MAC and ARP early returns (252, 253, 266). nfcs_ingress_dispatch_device runs
+ * between nfcs_l2_lookup_device and nfcs_l3_forward_device on the arrays those calls and the ingress ACL
+ * wrote; nfcs_switch_rx_device chains every stage of process_received_packet in one call. The symbols of this
+ * section were added without changing NFCS_ABI_VERSION (it stays 2): detect them by symbol lookup (dlsym
+ * "nfcs_ingress_dispatch_device"). */
+
+/* Where process_received_packet stops for a frame (d_class). */
+enum nfcs_sw_class {
+    NFCS_SW_UNHANDLED = 0,  /* no Ethernet header: "Unhandled packet type" (328)                          */
+    NFCS_SW_RX_DOWN = 1,    /* the ingress link is down, or ingress_port is no port of the fdb (215)      */
+    NFCS_SW_IN_DENY = 2,    /* the ingress ACL denies (226-229): an RX drop                               */
+    NFCS_SW_RED_OK = 3,     /* REDIRECT to a port below num_ports whose link is up (239-242)              */
+    NFCS_SW_RED_DOWN = 4,   /* REDIRECT to a port whose link is down (233): an RX drop                    */
+    NFCS_SW_RED_RANGE = 5,  /* REDIRECT to a port >= num_ports (233): an RX drop                          */
+    NFCS_SW_LLDP = 6,       /* outer EtherType 0x88CC (252)                                               */
+    NFCS_SW_ZERO_MAC = 7,   /* destination MAC 00:00:00:00:00:00, the reference's BPDU placeholder (253)  */
+    NFCS_SW_ARP = 8,        /* L3 EtherType 0x0806 (259-266)                                              */
+    NFCS_SW_LOCAL = 9,      /* NFCS_RT_LOCAL (270-276)                                                    */
+    NFCS_SW_TTL = 10,       /* NFCS_RT_TTL_EXPIRED (279)                                                  */
+    NFCS_SW_NO_ROUTE = 11,  /* NFCS_RT_NO_ROUTE (301)                                                     */
+    NFCS_SW_ARP_MISS = 12,  /* NFCS_RT_ARP_MISS (300)                                                     */
+    NFCS_SW_NO_IF_MAC = 13, /* NFCS_RT_NO_IF_MAC (292)                                                    */
+    NFCS_SW_L3_FWD = 14,    /* NFCS_RT_FORWARD: process_egress_pipeline on the route's interface (296)    */
+    NFCS_SW_L2_FWD = 15,    /* NFCS_L2_FORWARD (320)                                                      */
+    NFCS_SW_L2_FLOOD = 16,  /* NFCS_L2_FLOOD (323)                                                        */
+    NFCS_SW_SAME_PORT = 17, /* NFCS_L2_DROP_SAME_PORT (314)                                               */
+    NFCS_SW_LINK_DOWN = 18, /* NFCS_L2_DROP_LINK_DOWN (314)                                               */
+    NFCS_SW_STP = 19,       /* NFCS_L2_DROP_STP (315)                                                     */
+    NFCS_SW_VLAN = 20,      /* NFCS_L2_DROP_VLAN (316)                                                    */
+    NFCS_SW_BAD_DESC = 21   /* the descriptor reaches outside the arena: the frame is not read            */
+};
+
+/* InterfaceManager's RX counters of one port (_increment_rx_stats). */
+typedef struct nfcs_rx_stats {
+    uint64_t rx_packets, rx_bytes, rx_drops;
+} nfcs_rx_stats;
+#ifdef __cplusplus
+static_assert(sizeof(nfcs_rx_stats) == 24, "nfcs_rx_stats is a 24-byte record");
+#endif
+
+/* The dispatch over device-resident frames: one kernel, one lane per frame, read-only on the frames (bytes
+ * 0..15 of a permitted frame with len >= 14, bytes 16..19 as well with len >= 18; no other frame is read),
+ * asynchronous on the stream. Per frame, in the reference's order:
+ *  1. The ingress link is down (the fdb's state byte of ingress_port, 215) or ingress_port is at or above
+ *     the fdb's ports: NFCS_SW_RX_DOWN for every frame, everything MASKED (d_nh[i] = NFCS_NH_NONE,
+ *     d_l2_port[i] = NFCS_IF_NONE, d_l2_verdict[i] = NFCS_L2_SKIP), nothing counted.
+ *  2. Otherwise rx_packets += 1 and rx_bytes += len (216).
+ *  3. d_action[i] == NFCS_ACL_BAD_DESC, d_rt_verdict[i] == NFCS_RT_BAD_DESC or a descriptor that reaches
+ *     outside the arena: NFCS_SW_BAD_DESC, masked, not read, not a drop.
+ *  4. NFCS_ACL_DENY: NFCS_SW_IN_DENY (226-229). NFCS_ACL_REDIRECT with d_redirect[i] >= num_ports:
+ *     NFCS_SW_RED_RANGE; to a port whose link is down (or that the fdb does not know): NFCS_SW_RED_DOWN
+ *     (233). All three are masked and count rx_drops += 1 and, once more, rx_packets += 1 and rx_bytes += len:
+ *     _increment_rx_stats(port, len, false, true) at 228 and 235 adds to all three counters, so the
+ *     reference counts a dropped frame twice, and so does this call.
+ *  5. A valid REDIRECT: NFCS_SW_RED_OK, d_nh[i] = NFCS_NH_NONE, d_l2_port[i] = d_redirect[i],
+ *     d_l2_verdict[i] = NFCS_L2_SKIP, d_bypass[i] = 1 (239-240: process_egress and the enqueue on the
+ *     redirect port, no egress ACL).
+ *  6. NFCS_ACL_PERMIT with len >= 14, in this order: outer EtherType 0x88CC: NFCS_SW_LLDP (252); destination
+ *     MAC all zero: NFCS_SW_ZERO_MAC (253); L3 EtherType 0x0806: NFCS_SW_ARP (266), the L3 EtherType being the
+ *     inner one only when the outer is 0x8100 and len >= 18 (259-264). All three are masked.
+ *  7. Every other frame is live: the three in/out arrays keep their values and the class follows
+ *     d_rt_verdict[i], for NFCS_RT_NOT_IPV4 d_l2_verdict[i] (NFCS_SW_UNHANDLED without an Ethernet header).
+ *   d_action, d_redirect  n bytes / n u32 of nfcs_acl_eval_device; both may be NULL: the port has no ingress
+ *                         list and every frame is permitted. d_redirect alone NULL: every REDIRECT reads
+ *                         NFCS_SW_RED_RANGE.
+ *   d_rt_verdict          n bytes of nfcs_route_lookup_device, required
+ *   d_nh, d_l2_port, d_l2_verdict   IN/OUT, required; written only where stated (stores, no read-modify-write
+ *                         of other entries)
+ *   d_class, d_bypass     optional (NULL) n bytes each: NFCS_SW_*, and 1 for NFCS_SW_RED_OK else 0
+ *   d_rx_stats            optional (NULL) records indexed by port id, IN/OUT: d_rx_stats[ingress_port]
+ *                         accumulates across calls on the device, as d_depth does; no other record is
+ *                         touched. The sums are integers added atomically (one 64-bit atomic per counter per
+ *                         workgroup), so the result does not depend on the order.
+ * n == 0 returns NFCS_OK without a launch. fdb must be uploaded to ctx (else NFCS_EINVAL). */
+NFCS_API int nfcs_ingress_dispatch_device(nfcs_ctx* ctx, const nfcs_fdb* fdb, uint32_t ingress_port,
+                                          uint32_t num_ports, const uint8_t* d_arena, uint64_t arena_bytes,
+                                          const nfcs_desc* d_desc, uint32_t n, const uint8_t* d_action,
+                                          const uint32_t* d_redirect, const uint8_t* d_rt_verdict, uint32_t* d_nh,
+                                          uint32_t* d_l2_port, uint8_t* d_l2_verdict, uint8_t* d_class,
+                                          uint8_t* d_bypass, nfcs_rx_stats* d_rx_stats, void* stream);
+/* The same sequential walk on the CPU (host arrays, same meanings): the definition the kernel equals bit for
+ * bit (csrc/nfcs_switch.h). fdb must be committed. */
+NFCS_API int nfcs_ingress_dispatch_host(const nfcs_fdb* fdb, uint32_t ingress_port, uint32_t num_ports,
+                                        const uint8_t* arena, uint64_t arena_bytes, const nfcs_desc* desc, uint32_t n,
+                                        const uint8_t* action, const uint32_t* redirect, const uint8_t* rt_verdict,
+                                        uint32_t* nh, uint32_t* l2_port, uint8_t* l2_verdict, uint8_t* cls,
+                                        uint8_t* bypass, nfcs_rx_stats* rx_stats);
+
+/* nfcs_egress_acl_device over an item list whose redirected items bypass the ACL (switch.hpp:238-240).
+ *   d_item_src, d_bypass  both or neither (else NFCS_EINVAL): item i is BYPASSED when d_port[i] is not
+ *                         NFCS_IF_NONE, d_item_src[i] < n_src and d_bypass[d_item_src[i]] != 0 (d_bypass: n_src
+ *                         bytes of nfcs_ingress_dispatch_device, d_item_src of nfcs_flood_expand_device). A
+ *                         bypassed item keeps its port, its descriptor and frame are not looked at, it is
+ *                         counted nowhere, and d_action[i] = NFCS_ACL_BYPASS with NFCS_ACL_NO_MATCH.
+ * Everything else is nfcs_egress_acl_device, which is this call with both arrays NULL. */
+#define NFCS_ACL_BYPASS 5u
+NFCS_API int nfcs_egress_acl_items_device(nfcs_ctx* ctx, const nfcs_aclset* set, const uint8_t* d_arena,
+                                          uint64_t arena_bytes, const nfcs_desc* d_desc, uint32_t n, uint32_t* d_port,
+                                          const uint32_t* d_item_src, const uint8_t* d_bypass, uint32_t n_src,
+                                          uint8_t* d_action, uint32_t* d_rule, uint32_t* d_redirect,
+                                          uint32_t* d_denied_pkts, uint64_t* d_denied_bytes, void* stream);
+NFCS_API int nfcs_egress_acl_items_host(const nfcs_aclset* set, const uint8_t* arena, uint64_t arena_bytes,
+                                        const nfcs_desc* desc, uint32_t n, uint32_t* port, const uint32_t* item_src,
+                                        const uint8_t* bypass, uint32_t n_src, uint8_t* action, uint32_t* rule,
+                                        uint32_t* redirect, uint32_t* denied_pkts, uint64_t* denied_bytes);
+
+/* process_received_packet for one RX burst as ONE call: route lookup, ingress ACL (when tables.ingress_acl
+ * is given), L2 lookup, dispatch, fused forward, flood expand, egress plan, VLAN edit, egress ACL with bypass
+ * (when tables.aclset is given), enqueue and TX-queue append (when tables.txq is given), in that order on one
+ * stream, each stage exactly the call of its own section. No host synchronisation, no transfer: every
+ * intermediate array lives in the caller's workspace. The dequeue (the reference's TX loop) and the ICMP
+ * responder (the reference's call sites are comments) stay separate calls. */
+typedef struct nfcs_switch_tables {
+    const nfcs_fib* fib;         /* required */
+    const nfcs_acl* ingress_acl; /* NULL: the ingress port has no list                                      */
+    const nfcs_fdb* fdb;         /* required */
+    const nfcs_egress* egress;   /* required */
+    const nfcs_aclset* aclset;   /* NULL: no egress ACLs; d_denied_pkts / d_denied_bytes are not touched    */
+    nfcs_txq* txq;               /* NULL: no append                                                         */
+} nfcs_switch_tables;
+typedef struct nfcs_switch_rx_io {
+    /* the frames */
+    uint8_t* d_arena;            /* 16-byte aligned; frames in [0, copy_base), flood copies behind          */
+    uint64_t arena_bytes, copy_base;
+    uint32_t copy_align;         /* as in nfcs_flood_expand_device                                          */
+    uint32_t n, cap;             /* frames; item entries (an overflow is reported through d_totals)         */
+    uint32_t ingress_port, num_ports;
+    const nfcs_desc* d_desc;     /* n */
+    /* state that chains from burst to burst on the device */
+    uint32_t* d_depth;           /* keys u32, IN/OUT (nfcs_egress_enqueue_device)                           */
+    uint32_t* d_denied_pkts;     /* optional pair, IN/OUT (nfcs_egress_acl_device)                          */
+    uint64_t* d_denied_bytes;
+    nfcs_rx_stats* d_rx_stats;   /* optional, IN/OUT (nfcs_ingress_dispatch_device)                         */
+    /* outputs */
+    nfcs_desc* d_item_desc;      /* cap: the items' descriptors after the VLAN edit                         */
+    uint32_t* d_item_port;       /* cap: the items' FINAL ports, after the egress ACL                       */
+    uint32_t* d_item_src;        /* cap */
+    nfcs_flood_totals* d_totals; /* one record, 8-byte aligned                                              */
+    uint32_t* d_order;           /* cap */
+    uint32_t* d_key_start;       /* keys + 1 */
+    uint32_t* d_key_dropped;     /* optional keys u32 */
+    uint8_t* d_class;            /* optional n bytes NFCS_SW_* */
+    uint64_t handle_base;        /* the append's handle of item k is handle_base + k                        */
+    /* every intermediate array; nfcs_switch_rx_workspace_bytes(n, cap) bytes at least, 16-byte aligned     */
+    void* d_workspace;
+    uint64_t workspace_bytes;
+} nfcs_switch_rx_io;
+/* The workspace one nfcs_switch_rx_device call over n frames and cap items needs; every sub-array of it
+ * starts on a 16-byte boundary. */
+NFCS_API uint64_t nfcs_switch_rx_workspace_bytes(uint32_t n, uint32_t cap);
+/* NFCS_EINVAL, before anything is launched or written: a required table that is NULL or not uploaded to
+ * ctx's device, an optional one that is given but not uploaded, a txq of another context, a workspace that is
+ * NULL, misaligned or smaller than nfcs_switch_rx_workspace_bytes(n, cap), and every argument error of the
+ * stages (alignment, copy_base, copy_align, the counter pair). n == 0 returns NFCS_OK without a launch. The
+ * context's scratch grows on demand as in the stages (NFCS_ENOMEM leaves the context usable). */
+NFCS_API int nfcs_switch_rx_device(nfcs_ctx* ctx, const nfcs_switch_tables* tables, const nfcs_switch_rx_io* io,
+                                   void* stream);
 
 /* ---- flow-key extract + hash -------------------------------------------- */
 

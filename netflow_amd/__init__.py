@@ -107,6 +107,14 @@ assert EGRESS_PORT_DTYPE.itemsize == 16
 # the TX queues (include/nfcs.h nfcs_txq_*, NFCS_SCHED_*); WRR and DRR are the reference's one plain round-robin
 SCHED_STRICT_PRIORITY, SCHED_WRR, SCHED_DRR = range(3)
 
+# the ingress dispatch and the one-call RX pipeline (include/nfcs.h nfcs_sw_class, nfcs_rx_stats)
+(SW_UNHANDLED, SW_RX_DOWN, SW_IN_DENY, SW_RED_OK, SW_RED_DOWN, SW_RED_RANGE, SW_LLDP, SW_ZERO_MAC, SW_ARP, SW_LOCAL,
+ SW_TTL, SW_NO_ROUTE, SW_ARP_MISS, SW_NO_IF_MAC, SW_L3_FWD, SW_L2_FWD, SW_L2_FLOOD, SW_SAME_PORT, SW_LINK_DOWN, SW_STP,
+ SW_VLAN, SW_BAD_DESC) = range(22)
+ACL_BYPASS = 5  # egress_acl_items_*: the item's source frame was redirected by the ingress ACL
+RX_STATS_DTYPE = np.dtype([("rx_packets", "<u8"), ("rx_bytes", "<u8"), ("rx_drops", "<u8")])
+assert RX_STATS_DTYPE.itemsize == 24
+
 NEXTHOP_DTYPE = np.dtype([("dst_mac", "u1", (6,)), ("src_mac", "u1", (6,))])
 FLOW_KEY_DTYPE = np.dtype([("hash", "<u4"), ("vlan_id", "<u2"), ("ethertype", "<u2"),
                            ("src_mac", "u1", (6,)), ("dst_mac", "u1", (6,)), ("protocol", "u1"),
@@ -249,6 +257,12 @@ def _declare(L):
         "nfcs_aclset_eval_host": ([_vp, _u32, _vp, _u32] + [ctypes.POINTER(_u32)] * 3, ctypes.c_int),
         "nfcs_egress_acl_host": ([_vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
         "nfcs_egress_acl_device": ([_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+        "nfcs_ingress_dispatch_device": ([_vp, _vp, _u32, _u32, _vp, _u64, _vp, _u32] + [_vp] * 10, ctypes.c_int),
+        "nfcs_ingress_dispatch_host": ([_vp, _u32, _u32, _vp, _u64, _vp, _u32] + [_vp] * 9, ctypes.c_int),
+        "nfcs_egress_acl_items_device": ([_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u32] + [_vp] * 6, ctypes.c_int),
+        "nfcs_egress_acl_items_host": ([_vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u32] + [_vp] * 5, ctypes.c_int),
+        "nfcs_switch_rx_workspace_bytes": ([_u32, _u32], _u64),
+        "nfcs_switch_rx_device": ([_vp, _vp, _vp, _vp], ctypes.c_int),
         "nfcs_txq_create": ([_vp, _vp, ctypes.POINTER(_vp)], ctypes.c_int),
         "nfcs_txq_destroy": ([_vp], ctypes.c_int),
         "nfcs_txq_set_scheduler": ([_vp, _u32, _u32], ctypes.c_int),
@@ -518,6 +532,32 @@ class AclSet(_Table):
                                           cp(denied_pkts), cp(denied_bytes)), "nfcs_egress_acl_host")
         return {"port": port, "action": action, "rule": rule, "redirect": redirect}
 
+    def egress_acl_items_host(self, arena, desc, port, item_src=None, bypass=None, denied_pkts=None,
+                              denied_bytes=None) -> dict:
+        """nfcs_egress_acl_items_host: egress_acl_host over an item list whose items of redirected frames bypass
+        the ACL. item_src (n u32, flood_expand's) and bypass (one byte per source frame, ingress_dispatch's), both
+        or neither: an item with a port whose source frame is marked keeps its port, is not read or counted and
+        reads ACL_BYPASS. Without them it is egress_acl_host."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        desc = np.ascontiguousarray(desc, dtype=DESC_DTYPE)
+        port = np.array(port, dtype=np.uint32)
+        n = len(desc)
+        assert len(port) == n
+        item_src = None if item_src is None else np.ascontiguousarray(item_src, dtype=np.uint32)
+        bypass = None if bypass is None else np.ascontiguousarray(bypass, dtype=np.uint8)
+        assert item_src is None or len(item_src) == n
+        for a, dt in ((denied_pkts, np.uint32), (denied_bytes, np.uint64)):
+            assert a is None or (a.dtype == dt and a.flags.c_contiguous and a.flags.writeable)
+        action, rule, redirect = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        scratch = np.zeros(1, np.uint64)  # an array that was given stays given when it is empty
+        cp = lambda a: None if a is None else (a.ctypes.data if a.size else scratch.ctypes.data)
+        _check(lib().nfcs_egress_acl_items_host(self.ptr, arena.ctypes.data, arena.nbytes, desc.ctypes.data, n,
+                                                port.ctypes.data, cp(item_src), cp(bypass),
+                                                0 if bypass is None else len(bypass), action.ctypes.data,
+                                                rule.ctypes.data, redirect.ctypes.data, cp(denied_pkts),
+                                                cp(denied_bytes)), "nfcs_egress_acl_items_host")
+        return {"port": port, "action": action, "rule": rule, "redirect": redirect}
+
 
 class Fdb(_Table):
     """The L2 forwarding database and port state behind Engine.l2_lookup_device (nfcs_fdb): FDB_ENTRY_DTYPE
@@ -596,6 +636,35 @@ class Fdb(_Table):
                                             int(cap), dp(item_desc), dp(item_port), dp(item_src), totals.ctypes.data),
                "nfcs_flood_expand_host")
         return {"item_desc": item_desc, "item_port": item_port, "item_src": item_src, "totals": totals[0]}
+
+    def ingress_dispatch_host(self, ingress_port: int, num_ports: int, arena, arena_bytes: int, desc, rt_verdict, nh,
+                              l2_port, l2_verdict, action=None, redirect=None, rx_stats=None, want_class: bool = True,
+                              want_bypass: bool = True) -> dict:
+        """The sequential walk behind Engine.ingress_dispatch_device, on the CPU (nfcs_ingress_dispatch_host): what
+        process_received_packet does between the stages for one RX burst of ingress_port. action / redirect (the
+        ingress ACL's; None: no list, every frame permitted), rt_verdict, and nh / l2_port / l2_verdict as the
+        route lookup, the ACL and the L2 lookup left them. Returns copies of nh, l2_port and l2_verdict with the
+        masks applied, cls (n bytes SW_*) and bypass (n bytes; None where not wanted). rx_stats (RX_STATS_DTYPE
+        records indexed by port) is updated in place."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        desc = np.ascontiguousarray(desc, dtype=DESC_DTYPE)
+        n = len(desc)
+        arr = lambda a, dt: None if a is None else np.ascontiguousarray(a, dtype=dt)
+        action, redirect, rt_verdict = arr(action, np.uint8), arr(redirect, np.uint32), arr(rt_verdict, np.uint8)
+        nh, l2_port, l2_verdict = np.array(nh, np.uint32), np.array(l2_port, np.uint32), np.array(l2_verdict, np.uint8)
+        if any(a is not None and len(a) != n for a in (action, redirect, rt_verdict, nh, l2_port, l2_verdict)):
+            raise NfcsError("ingress_dispatch_host: every per-packet array needs n entries")
+        assert rx_stats is None or (rx_stats.dtype == RX_STATS_DTYPE and rx_stats.flags.c_contiguous and
+                                    rx_stats.flags.writeable and len(rx_stats) > ingress_port)
+        cls = np.zeros(n, np.uint8) if want_class else None
+        bypass = np.zeros(n, np.uint8) if want_bypass else None
+        scratch = np.zeros(1, np.uint64)  # an array that was given stays given when n is 0
+        dp = lambda a: None if a is None else (a.ctypes.data if a.size else scratch.ctypes.data)
+        _check(lib().nfcs_ingress_dispatch_host(self.ptr, int(ingress_port), int(num_ports), dp(arena), int(arena_bytes),
+                                                dp(desc), n, dp(action), dp(redirect), dp(rt_verdict), dp(nh), dp(l2_port),
+                                                dp(l2_verdict), dp(cls), dp(bypass), dp(rx_stats)),
+               "nfcs_ingress_dispatch_host")
+        return {"nh": nh, "l2_port": l2_port, "l2_verdict": l2_verdict, "cls": cls, "bypass": bypass}
 
 
 class Icmp(_Table):
@@ -804,6 +873,25 @@ def txq_closed_form_host(sched: int, depth, last: int, budget: int, want_seq: bo
                                            take.ctypes.data if nq else None, ctypes.byref(new_last),
                                            seq.ctypes.data if cap else None, cap), "nfcs_txq_closed_form_host")
     return take, int(new_last.value), seq if want_seq else None
+
+
+class _SwitchTables(ctypes.Structure):  # nfcs_switch_tables
+    _fields_ = [(k, _vp) for k in ("fib", "ingress_acl", "fdb", "egress", "aclset", "txq")]
+
+
+class _SwitchRxIo(ctypes.Structure):  # nfcs_switch_rx_io
+    _fields_ = ([("d_arena", _vp), ("arena_bytes", _u64), ("copy_base", _u64)] +
+                [(k, _u32) for k in ("copy_align", "n", "cap", "ingress_port", "num_ports")] +
+                [(k, _vp) for k in ("d_desc", "d_depth", "d_denied_pkts", "d_denied_bytes", "d_rx_stats", "d_item_desc",
+                                    "d_item_port", "d_item_src", "d_totals", "d_order", "d_key_start", "d_key_dropped",
+                                    "d_class")] +
+                [("handle_base", _u64), ("d_workspace", _vp), ("workspace_bytes", _u64)])
+
+
+def switch_rx_workspace_bytes(n: int, cap: int) -> int:
+    """nfcs_switch_rx_workspace_bytes: the device workspace one Engine.switch_rx_device call over n frames and
+    cap items needs."""
+    return int(lib().nfcs_switch_rx_workspace_bytes(int(n), int(cap)))
 
 
 class DeviceBuffer:
@@ -1079,6 +1167,55 @@ class Engine:
         _check(lib().nfcs_egress_acl_device(self.ctx, aclset.ptr, ptr(arena), arena_bytes, ptr(desc), n, ptr(port),
                                             ptr(action), ptr(rule), ptr(redirect), ptr(denied_pkts), ptr(denied_bytes),
                                             stream), "nfcs_egress_acl_device")
+
+    def ingress_dispatch_device(self, fdb: "Fdb", ingress_port: int, num_ports: int, arena, arena_bytes: int, desc,
+                                n: int, rt_verdict, nh, l2_port, l2_verdict, action=None, redirect=None, cls=None,
+                                bypass=None, rx_stats=None, stream=None):
+        """What process_received_packet does between the stages, per frame of one RX burst of ingress_port
+        (nfcs_ingress_dispatch_device), between l2_lookup_device and l3_forward_device: the ingress link test,
+        DENY / REDIRECT and the LLDP / zero-MAC / ARP early returns masking nh, l2_port and l2_verdict (in/out), a
+        valid REDIRECT's port into l2_port, and the RX counters. action (n bytes) and redirect (n u32) are
+        acl_eval_device's (None: the port has no ingress list); cls (n bytes SW_*), bypass (n bytes, for
+        egress_acl_items_device) and rx_stats (RX_STATS_DTYPE records indexed by port, accumulating) optional."""
+        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
+        _check(lib().nfcs_ingress_dispatch_device(self.ctx, fdb.ptr, int(ingress_port), int(num_ports), ptr(arena),
+                                                  arena_bytes, ptr(desc), n, ptr(action), ptr(redirect), ptr(rt_verdict),
+                                                  ptr(nh), ptr(l2_port), ptr(l2_verdict), ptr(cls), ptr(bypass),
+                                                  ptr(rx_stats), stream), "nfcs_ingress_dispatch_device")
+
+    def egress_acl_items_device(self, aclset: "AclSet", arena, arena_bytes: int, desc, n: int, port, action,
+                                item_src=None, bypass=None, n_src: int = 0, rule=None, redirect=None,
+                                denied_pkts=None, denied_bytes=None, stream=None):
+        """egress_acl_device over an item list whose items of redirected frames bypass the ACL
+        (nfcs_egress_acl_items_device): item_src (n u32, flood_expand_device's) and bypass (n_src bytes,
+        ingress_dispatch_device's), both or neither. A bypassed item keeps its port and reads ACL_BYPASS."""
+        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
+        _check(lib().nfcs_egress_acl_items_device(self.ctx, aclset.ptr, ptr(arena), arena_bytes, ptr(desc), n, ptr(port),
+                                                  ptr(item_src), ptr(bypass), int(n_src), ptr(action), ptr(rule),
+                                                  ptr(redirect), ptr(denied_pkts), ptr(denied_bytes), stream),
+               "nfcs_egress_acl_items_device")
+
+    def switch_rx_device(self, fib: Fib, fdb: "Fdb", egress: "Egress", ingress_port: int, num_ports: int, arena,
+                         arena_bytes: int, copy_base: int, copy_align: int, desc, n: int, cap: int, depth, item_desc,
+                         item_port, item_src, totals, order, key_start, workspace, workspace_bytes: int,
+                         ingress_acl: "Acl | None" = None, aclset: "AclSet | None" = None,
+                         txq: "TxQueues | None" = None, denied_pkts=None, denied_bytes=None, rx_stats=None,
+                         key_dropped=None, cls=None, handle_base: int = 0, stream=None):
+        """Switch::process_received_packet for one RX burst as one call on one stream, with no host step
+        (nfcs_switch_rx_device): route lookup, ingress ACL, L2 lookup, dispatch, forward, flood expand, plan,
+        VLAN edit, egress ACL with bypass, enqueue and, with txq, the append (handle of item k: handle_base + k).
+        depth, denied_pkts / denied_bytes and rx_stats chain on the device from burst to burst; item_desc,
+        item_port (final, after the egress ACL), item_src, totals, order, key_start, key_dropped and cls are the
+        outputs; workspace: switch_rx_workspace_bytes(n, cap) bytes of device memory."""
+        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
+        hp = lambda t: None if t is None else t.ptr
+        tb = _SwitchTables(hp(fib), hp(ingress_acl), hp(fdb), hp(egress), hp(aclset), hp(txq))
+        io = _SwitchRxIo(ptr(arena), int(arena_bytes), int(copy_base), int(copy_align), int(n), int(cap),
+                         int(ingress_port), int(num_ports), ptr(desc), ptr(depth), ptr(denied_pkts), ptr(denied_bytes),
+                         ptr(rx_stats), ptr(item_desc), ptr(item_port), ptr(item_src), ptr(totals), ptr(order),
+                         ptr(key_start), ptr(key_dropped), ptr(cls), int(handle_base), ptr(workspace),
+                         int(workspace_bytes))
+        _check(lib().nfcs_switch_rx_device(self.ctx, ctypes.byref(tb), ctypes.byref(io), stream), "nfcs_switch_rx_device")
 
     def txq_append_device(self, txq: "TxQueues", order, key_start, depth, n: int, handle=None, desc=None, stream=None):
         """enqueue_packet's emplace_back for the burst on the device copy of txq, after egress_enqueue_device

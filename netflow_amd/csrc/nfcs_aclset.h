@@ -132,14 +132,19 @@ inline void aclset_decide(const AclSetTables& t, uint32_t port, const uint8_t* f
     if (redirect_port) *redirect_port = r == NFCS_ACL_NO_MATCH ? NFCS_IF_NONE : t.act[r].redirect;
 }
 
-// nfcs_egress_acl_host: the burst in order (the order matters to nothing: the counters are sums).
+// nfcs_egress_acl_host: the burst in order (the order matters to nothing: the counters are sums). With item_src
+// and bypass (n_src bytes) it is nfcs_egress_acl_items_host: an item of a redirected frame keeps its port unread
+// and uncounted (switch.hpp:238-240).
 inline void aclset_egress(const AclSetTables& t, const uint8_t* arena, uint64_t arena_bytes, const nfcs_desc* desc,
                           uint32_t n, uint32_t* port, uint8_t* action, uint32_t* rule, uint32_t* redirect,
-                          uint32_t* denied_pkts, uint64_t* denied_bytes) {
+                          uint32_t* denied_pkts, uint64_t* denied_bytes, const uint32_t* item_src = nullptr,
+                          const uint8_t* bypass = nullptr, uint32_t n_src = 0) {
     for (uint32_t i = 0; i < n; ++i) {
         uint32_t a = NFCS_ACL_NO_PORT, r = NFCS_ACL_NO_MATCH, rp = NFCS_IF_NONE;
         const uint32_t pt = port[i];
-        if (pt != NFCS_IF_NONE) {
+        if (pt != NFCS_IF_NONE && item_src && bypass && item_src[i] < n_src && bypass[item_src[i]]) {
+            a = NFCS_ACL_BYPASS;
+        } else if (pt != NFCS_IF_NONE) {
             const uint64_t off = (uint64_t)desc[i].off16 * 16u, len = desc[i].len;
             if (off + ((len + 15u) & ~15ull) > arena_bytes) {
                 a = NFCS_ACL_BAD_DESC;

@@ -2059,6 +2059,183 @@ NFCS_API int nfcs_txq_closed_form_host(uint32_t sched, uint32_t num_queues, uint
     return NFCS_OK;
 }
 
+// ---- Ingress dispatch (nfcs_switch.h: the per-frame decision and the host walk) and the RX pipeline ------
+
+NFCS_API int nfcs_ingress_dispatch_host(const nfcs_fdb* f, uint32_t ingress_port, uint32_t num_ports, const uint8_t* arena,
+                                        uint64_t arena_bytes, const nfcs_desc* desc, uint32_t n, const uint8_t* action,
+                                        const uint32_t* redirect, const uint8_t* rt_verdict, uint32_t* nh,
+                                        uint32_t* l2_port, uint8_t* l2_verdict, uint8_t* cls, uint8_t* bypass,
+                                        nfcs_rx_stats* rx_stats) {
+    if (!f || !f->committed) return NFCS_EINVAL;
+    if (n == 0) return NFCS_OK;
+    if (!arena || !desc || !rt_verdict || !nh || !l2_port || !l2_verdict) return NFCS_EINVAL;
+    nfcs::sw_dispatch(f->t.port_state.data(), f->t.ports, ingress_port, num_ports, arena, arena_bytes, desc, n, action,
+                      redirect, rt_verdict, nh, l2_port, l2_verdict, cls, bypass, rx_stats);
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_ingress_dispatch_device(nfcs_ctx* c, const nfcs_fdb* f, uint32_t ingress_port, uint32_t num_ports,
+                                          const uint8_t* d_arena, uint64_t arena_bytes, const nfcs_desc* d_desc,
+                                          uint32_t n, const uint8_t* d_action, const uint32_t* d_redirect,
+                                          const uint8_t* d_rt_verdict, uint32_t* d_nh, uint32_t* d_l2_port,
+                                          uint8_t* d_l2_verdict, uint8_t* d_class, uint8_t* d_bypass,
+                                          nfcs_rx_stats* d_rx_stats, void* stream) {
+    if (!usable(c, f)) return NFCS_EINVAL;
+    DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    if (n == 0) return NFCS_OK;
+    if (!d_arena || !d_desc || !d_rt_verdict || !d_nh || !d_l2_port || !d_l2_verdict || ((uintptr_t)d_arena & 15u))
+        return NFCS_EINVAL;
+    if (((uintptr_t)d_redirect & 3u) || ((uintptr_t)d_nh & 3u) || ((uintptr_t)d_l2_port & 3u) ||
+        ((uintptr_t)d_rx_stats & 7u))
+        return NFCS_EINVAL;
+    const nfcs::DispatchArgs a{d_arena, arena_bytes, ingress_port, num_ports, n, d_desc, d_action, d_redirect,
+                               d_rt_verdict, d_nh, d_l2_port, d_l2_verdict, d_class, d_bypass, d_rx_stats};
+    NFCS_HIP(nfcs::launch_ingress_dispatch(c->di, f->dev, a, pick(c, stream)));
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_egress_acl_items_host(const nfcs_aclset* s, const uint8_t* arena, uint64_t arena_bytes,
+                                        const nfcs_desc* desc, uint32_t n, uint32_t* port, const uint32_t* item_src,
+                                        const uint8_t* bypass, uint32_t n_src, uint8_t* action, uint32_t* rule,
+                                        uint32_t* redirect, uint32_t* denied_pkts, uint64_t* denied_bytes) {
+    if (!s || !s->committed || (!denied_pkts != !denied_bytes) || (!item_src != !bypass)) return NFCS_EINVAL;
+    if (n == 0) return NFCS_OK;
+    if (!arena || !desc || !port || !action) return NFCS_EINVAL;
+    nfcs::aclset_egress(s->t, arena, arena_bytes, desc, n, port, action, rule, redirect, denied_pkts, denied_bytes,
+                        item_src, bypass, n_src);
+    return NFCS_OK;
+}
+
+NFCS_API int nfcs_egress_acl_items_device(nfcs_ctx* c, const nfcs_aclset* s, const uint8_t* d_arena, uint64_t arena_bytes,
+                                          const nfcs_desc* d_desc, uint32_t n, uint32_t* d_port,
+                                          const uint32_t* d_item_src, const uint8_t* d_bypass, uint32_t n_src,
+                                          uint8_t* d_action, uint32_t* d_rule, uint32_t* d_redirect,
+                                          uint32_t* d_denied_pkts, uint64_t* d_denied_bytes, void* stream) {
+    if (!usable(c, s)) return NFCS_EINVAL;
+    if ((!d_denied_pkts != !d_denied_bytes) || (!d_item_src != !d_bypass)) return NFCS_EINVAL;
+    DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    if (n == 0) return NFCS_OK;
+    if (!d_arena || !d_desc || !d_port || !d_action || ((uintptr_t)d_arena & 15u)) return NFCS_EINVAL;
+    if (((uintptr_t)d_port & 3u) || ((uintptr_t)d_rule & 3u) || ((uintptr_t)d_redirect & 3u) ||
+        ((uintptr_t)d_denied_pkts & 3u) || ((uintptr_t)d_denied_bytes & 7u) || ((uintptr_t)d_item_src & 3u))
+        return NFCS_EINVAL;
+    NFCS_HIP(nfcs::launch_egress_acl(c->di, s->dev, d_arena, arena_bytes, d_desc, n, d_port, d_action, d_rule, d_redirect,
+                                     d_denied_pkts, d_denied_bytes, pick(c, stream), d_item_src, d_bypass, n_src));
+    return NFCS_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// nfcs_switch_rx_device's workspace: every intermediate array of the chain, each on a 16-byte boundary.
+struct RxWorkspace {
+    uint64_t nh, eif, red, l2p, iport, ops, vlan, rt, st, act, l2v, byp, queue, eact, total;
+};
+RxWorkspace rx_workspace(uint32_t n, uint32_t cap) {
+    uint64_t at = 0;
+    auto part = [&at](uint64_t bytes) {
+        const uint64_t o = at;
+        at += (bytes + 15u) & ~15ull;
+        return o;
+    };
+    RxWorkspace w;
+    w.nh = part(4ull * n), w.eif = part(4ull * n), w.red = part(4ull * n), w.l2p = part(4ull * n);
+    w.iport = part(4ull * cap), w.ops = part(4ull * cap), w.vlan = part(2ull * n);
+    w.rt = part(n), w.st = part(n), w.act = part(n), w.l2v = part(n), w.byp = part(n);
+    w.queue = part(cap), w.eact = part(cap);
+    w.total = at;
+    return w;
+}
+}  // namespace
+
+extern "C" {
+
+NFCS_API uint64_t nfcs_switch_rx_workspace_bytes(uint32_t n, uint32_t cap) { return rx_workspace(n, cap).total; }
+
+NFCS_API int nfcs_switch_rx_device(nfcs_ctx* c, const nfcs_switch_tables* tb, const nfcs_switch_rx_io* io, void* stream) {
+    if (!c || !tb || !io) return NFCS_EINVAL;
+    // every table and every argument is tested before the first launch
+    if (!usable(c, tb->fib) || !usable(c, tb->fdb) || !usable(c, tb->egress)) return NFCS_EINVAL;
+    if ((tb->ingress_acl && !usable(c, tb->ingress_acl)) || (tb->aclset && !usable(c, tb->aclset))) return NFCS_EINVAL;
+    if (tb->txq && tb->txq->ctx != c) return NFCS_EINVAL;
+    const uint32_t n = io->n, cap = io->cap;
+    const RxWorkspace w = rx_workspace(n, cap);
+    if (!nfcs::flood_args_ok(io->num_ports, io->arena_bytes, io->copy_base, io->copy_align, n, true, true, true, true, true))
+        return NFCS_EINVAL;  // the expand's five input arrays are the workspace's: all given
+    if (!io->d_denied_pkts != !io->d_denied_bytes) return NFCS_EINVAL;
+    if (tb->txq && tb->txq->dev.keys != tb->egress->dev.keys) return NFCS_EINVAL;  // another egress table's queues
+    DeviceGuard dg_(c->di.device);  // the context's device on this thread, restored on return
+    if (dg_.err != hipSuccess) return hip_fail(dg_.err);
+    if (n == 0) return NFCS_OK;
+    if (!io->d_workspace || ((uintptr_t)io->d_workspace & 15u) || io->workspace_bytes < w.total) return NFCS_EINVAL;
+    if (!io->d_arena || !io->d_desc || !io->d_totals || ((uintptr_t)io->d_arena & 15u) || ((uintptr_t)io->d_totals & 7u) ||
+        ((uintptr_t)io->d_desc & 7u))
+        return NFCS_EINVAL;
+    if (cap > 0 && (!io->d_item_desc || !io->d_item_port || !io->d_item_src || !io->d_order)) return NFCS_EINVAL;
+    if (!io->d_key_start || (tb->egress->dev.keys > 0 && !io->d_depth)) return NFCS_EINVAL;
+    if (((uintptr_t)io->d_item_desc & 7u) || ((uintptr_t)io->d_item_port & 3u) || ((uintptr_t)io->d_item_src & 3u) ||
+        ((uintptr_t)io->d_order & 3u) || ((uintptr_t)io->d_key_start & 3u) || ((uintptr_t)io->d_key_dropped & 3u) ||
+        ((uintptr_t)io->d_depth & 3u) || ((uintptr_t)io->d_denied_pkts & 3u) || ((uintptr_t)io->d_denied_bytes & 7u) ||
+        ((uintptr_t)io->d_rx_stats & 7u))
+        return NFCS_EINVAL;
+    hipStream_t st = pick(c, stream);
+    uint8_t* ws = (uint8_t*)io->d_workspace;
+    uint32_t *d_nh = (uint32_t*)(ws + w.nh), *d_eif = (uint32_t*)(ws + w.eif), *d_red = (uint32_t*)(ws + w.red);
+    uint32_t *d_l2p = (uint32_t*)(ws + w.l2p), *d_iport = (uint32_t*)(ws + w.iport), *d_ops = (uint32_t*)(ws + w.ops);
+    uint16_t* d_vlan = (uint16_t*)(ws + w.vlan);
+    uint8_t *d_rt = ws + w.rt, *d_st = ws + w.st, *d_act = ws + w.act, *d_l2v = ws + w.l2v, *d_byp = ws + w.byp;
+    uint8_t *d_queue = ws + w.queue, *d_eact = ws + w.eact;
+    const bool acl = tb->ingress_acl != nullptr;
+    const uint64_t frames = io->copy_base;  // the frames lie in [0, copy_base); the copies behind are the egress side's
+    // 1-3: the three decisions (switch.hpp:219-245, 259-301, 305-326)
+    NFCS_HIP(nfcs::launch_route_lookup(c->di, tb->fib->dev, io->d_arena, frames, io->d_desc, n, d_nh, d_eif, d_rt, st));
+    if (acl)
+        NFCS_HIP(nfcs::launch_acl_eval(c->di, tb->ingress_acl->dev, io->d_arena, frames, io->d_desc, n, d_act, nullptr,
+                                       d_red, d_nh, st));
+    NFCS_HIP(nfcs::launch_l2_lookup(c->di, tb->fdb->dev, io->ingress_port, io->d_arena, frames, io->d_desc, n, d_rt, d_l2p,
+                                    d_l2v, d_vlan, nullptr, st));
+    // 4: what the switch does between them
+    const nfcs::DispatchArgs da{io->d_arena, frames, io->ingress_port, io->num_ports, n, io->d_desc,
+                                acl ? d_act : nullptr, acl ? d_red : nullptr, d_rt, d_nh, d_l2p, d_l2v, io->d_class, d_byp,
+                                io->d_rx_stats};
+    NFCS_HIP(nfcs::launch_ingress_dispatch(c->di, tb->fdb->dev, da, st));
+    // 5: the fused forward
+    int rc = l3_forward_device(c, io->d_arena, frames, io->d_desc, d_nh, n, tb->fib->d_table, tb->fib->d_table_n, d_st, st);
+    if (rc != NFCS_OK) return rc;
+    // 6: the item list and the flood copies
+    const nfcs::FloodArgs fa{io->d_arena, io->arena_bytes, io->copy_base, io->copy_align, io->ingress_port, io->num_ports,
+                             n, cap, io->d_desc, d_eif, d_st, d_l2p, d_l2v, d_vlan, io->d_item_desc, d_iport,
+                             io->d_item_src, io->d_totals};
+    rc = with_eq_scratch(c, nfcs::flood_scratch_words(n), st, [&](uint32_t* sc) {
+        return nfcs::launch_flood_expand(c->di, tb->fdb->dev, fa, sc, st);
+    });
+    if (rc != NFCS_OK || cap == 0) return rc;
+    // 7-9: process_egress_pipeline over the items (113-139); the plan writes the ports the ACL then edits
+    NFCS_HIP(nfcs::launch_egress_plan(c->di, tb->egress->dev, io->d_arena, io->arena_bytes, io->d_item_desc, cap, nullptr,
+                                      nullptr, d_iport, io->d_item_port, d_ops, d_queue, st));
+    {
+        const Shape sh = launch_shape(c, io->arena_bytes, io->d_item_desc, cap, kVlanRule);
+        NFCS_HIP(nfcs::launch_vlan(c->di, io->d_arena, io->arena_bytes, io->d_item_desc, cap, d_ops, 0u, nullptr, 0u, nullptr,
+                                   st, sh.mean, sh.obs, sh.bits));
+    }
+    if (tb->aclset)
+        NFCS_HIP(nfcs::launch_egress_acl(c->di, tb->aclset->dev, io->d_arena, io->arena_bytes, io->d_item_desc, cap,
+                                         io->d_item_port, d_eact, nullptr, nullptr, io->d_denied_pkts, io->d_denied_bytes,
+                                         st, io->d_item_src, d_byp, n));
+    // 10-11: enqueue_packet (qos_manager.cpp:111-153)
+    rc = with_eq_scratch(c, nfcs::egress_scratch_words(cap, tb->egress->dev.keys), st, [&](uint32_t* sc) {
+        return nfcs::launch_egress_enqueue(c->di, tb->egress->dev, io->d_item_port, d_queue, cap, io->d_depth, nullptr,
+                                           io->d_order, io->d_key_start, io->d_key_dropped, sc, st);
+    });
+    if (rc != NFCS_OK) return rc;
+    if (tb->txq)
+        NFCS_HIP(nfcs::launch_txq_append(tb->txq->dev, io->d_order, io->d_key_start, io->d_depth, nullptr, nullptr, cap, st,
+                                         io->handle_base));
+    return NFCS_OK;
+}
+
 NFCS_API int nfcs_update_host(nfcs_ctx* c, uint8_t* h_arena, uint64_t arena_bytes,
                               const nfcs_desc* h_desc, uint32_t n, uint8_t* h_status,
                               uint32_t flags) {

@@ -12,6 +12,7 @@
 #include "nfcs_fdb.h"
 #include "nfcs_fib.h"
 #include "nfcs_icmp.h"
+#include "nfcs_switch.h"
 #include "nfcs_txq.h"
 
 namespace nfcs {
@@ -255,9 +256,12 @@ struct AclSetDev {
     uint32_t ports = 0, rules_padded = 0;
 };
 
+// item_src / bypass (both or neither; bypass holds n_src bytes): the items whose source frame is marked bypass
+// the ACL (nfcs_egress_acl_items_device).
 hipError_t launch_egress_acl(const DevInfo& di, const AclSetDev& set, const uint8_t* arena, uint64_t arena_bytes,
                              const nfcs_desc* desc, uint32_t n, uint32_t* port, uint8_t* action, uint32_t* rule,
-                             uint32_t* redirect, uint32_t* denied_pkts, uint64_t* denied_bytes, hipStream_t stream);
+                             uint32_t* redirect, uint32_t* denied_pkts, uint64_t* denied_bytes, hipStream_t stream,
+                             const uint32_t* item_src = nullptr, const uint8_t* bypass = nullptr, uint32_t n_src = 0);
 
 // The committed L2 tables in device memory (nfcs_fdb_upload; the arrays of FdbTables, nfcs_fdb.h).
 struct FdbDev {
@@ -281,6 +285,24 @@ struct EgressDev {
     const uint4* recs = nullptr;  // ports 16-byte records {flags, native, queues, max_depth}, 16-byte aligned
     uint32_t ports = 0, keys = 0;
 };
+
+// The ingress dispatch (nfcs_switch.h sw_classify is the per-frame definition).
+struct DispatchArgs {
+    const uint8_t* arena;
+    uint64_t arena_bytes;
+    uint32_t ingress, num_ports, n;
+    const nfcs_desc* desc;
+    const uint8_t* action;
+    const uint32_t* redirect;
+    const uint8_t* rt_verdict;
+    uint32_t* nh;
+    uint32_t* l2_port;
+    uint8_t* l2_verdict;
+    uint8_t* cls;
+    uint8_t* bypass;
+    nfcs_rx_stats* rx_stats;
+};
+hipError_t launch_ingress_dispatch(const DevInfo& di, const FdbDev& fdb, const DispatchArgs& a, hipStream_t stream);
 
 hipError_t launch_egress_plan(const DevInfo& di, const EgressDev& eg, const uint8_t* arena, uint64_t arena_bytes,
                               const nfcs_desc* desc, uint32_t n, const uint32_t* l3_port, const uint8_t* fwd_status,
@@ -319,7 +341,8 @@ constexpr uint32_t kTxqPlanThreads = NFCS_L2_MAX_PORTS;  // one lane per port, o
 static_assert(kTxqPlanThreads == 1024u, "the plan is one workgroup of 16 waves");
 
 hipError_t launch_txq_append(const TxqDev& t, const uint32_t* order, const uint32_t* key_start, const uint32_t* depth,
-                             const uint64_t* handle, const nfcs_desc* desc, uint32_t n, hipStream_t stream);
+                             const uint64_t* handle, const nfcs_desc* desc, uint32_t n, hipStream_t stream,
+                             uint64_t handle_base = 0);  // handle and desc both null: packet i is handle_base + i
 hipError_t launch_txq_dequeue(const TxqDev& t, const uint32_t* budget, uint32_t budget_all, uint32_t* depth,
                               uint64_t* tx, uint32_t tx_cap, uint8_t* tx_queue, uint32_t* tx_start, uint32_t* dequeued,
                               hipStream_t stream);

@@ -2493,7 +2493,9 @@ __global__ __launch_bounds__(kBlock) void egress_acl_kernel(const nfcs_desc* __r
                                                             uint32_t* __restrict__ rule_out,
                                                             uint32_t* __restrict__ redirect_out,
                                                             uint32_t* __restrict__ denied_pkts,
-                                                            unsigned long long* __restrict__ denied_bytes) {
+                                                            unsigned long long* __restrict__ denied_bytes,
+                                                            const uint32_t* __restrict__ item_src,
+                                                            const uint8_t* __restrict__ bypass, uint32_t n_src) {
     extern __shared__ __attribute__((aligned(16))) uint8_t ea_lds[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint64_t p0 = ((uint64_t)xcd_block_n(nblocks) * kWavesPerBlock + rfl(wave)) * 64u;
@@ -2507,8 +2509,14 @@ __global__ __launch_bounds__(kBlock) void egress_acl_kernel(const nfcs_desc* __r
         port = port_io[p];
     }
     const bool has_port = port != NFCS_IF_NONE;  // false past n; without a port the descriptor means nothing
+    // an item of a redirected frame bypasses the ACL (switch.hpp:238-240): it keeps its port unread and uncounted
+    bool byp = false;
+    if (item_src && has_port) {
+        const uint32_t src = item_src[p];
+        if (src < n_src) byp = bypass[src] != 0;
+    }
     const uint64_t off = (uint64_t)dl.x * 16u;
-    const bool live = has_port && off + (((uint64_t)dl.y + 15u) & ~15ull) <= arena_bytes;
+    const bool live = has_port && !byp && off + (((uint64_t)dl.y + 15u) & ~15ull) <= arena_bytes;
     uint2 bind = make_uint2(0u, 0u);
     if (live && port < set.ports) bind = set.bind[port];
     const bool scan = bind.y != 0u;  // the frame is read only for these
@@ -2640,7 +2648,7 @@ __global__ __launch_bounds__(kBlock) void egress_acl_kernel(const nfcs_desc* __r
             }
         }
     }
-    uint32_t action = !has_port ? NFCS_ACL_NO_PORT : live ? NFCS_ACL_PERMIT : NFCS_ACL_BAD_DESC;
+    uint32_t action = !has_port ? NFCS_ACL_NO_PORT : byp ? NFCS_ACL_BYPASS : live ? NFCS_ACL_PERMIT : NFCS_ACL_BAD_DESC;
     uint32_t redirect = NFCS_IF_NONE, rule = NFCS_ACL_NO_MATCH;
     if (match != NFCS_ACL_NO_MATCH) {  // a scanned lane; match < set.rules_padded and no padding rule matches
         const uint2 a = set.act[match];
@@ -2684,14 +2692,16 @@ __global__ __launch_bounds__(kBlock) void egress_acl_kernel(const nfcs_desc* __r
 
 hipError_t launch_egress_acl(const DevInfo& di, const AclSetDev& set, const uint8_t* arena, uint64_t arena_bytes,
                              const nfcs_desc* desc, uint32_t n, uint32_t* port, uint8_t* action, uint32_t* rule,
-                             uint32_t* redirect, uint32_t* denied_pkts, uint64_t* denied_bytes, hipStream_t stream) {
+                             uint32_t* redirect, uint32_t* denied_pkts, uint64_t* denied_bytes, hipStream_t stream,
+                             const uint32_t* item_src, const uint8_t* bypass, uint32_t n_src) {
     (void)di;
     if (n == 0) return hipSuccess;
+    if (!item_src || !bypass) item_src = nullptr, bypass = nullptr, n_src = 0;
     // 64 packets per wave, one lane each, XCD-aware order; LDS: the header rows, the sum slots, then the rules
     const uint32_t g = (n + 255u) / 256u;
     const unsigned lds = kAclRowsBytes + kEaSlotsBytes + set.rules_padded * (unsigned)sizeof(AclRec);
     hipLaunchKernelGGL(egress_acl_kernel, dim3(g), dim3(kBlock), lds, stream, desc, n, g, arena, arena_bytes, port, set,
-                       action, rule, redirect, denied_pkts, (unsigned long long*)denied_bytes);
+                       action, rule, redirect, denied_pkts, (unsigned long long*)denied_bytes, item_src, bypass, n_src);
     return hipGetLastError();
 }
 
@@ -2890,6 +2900,109 @@ hipError_t launch_egress_plan(const DevInfo& di, const EgressDev& eg, const uint
     const uint32_t g = (n + 255u) / 256u;
     hipLaunchKernelGGL(egress_plan_kernel, dim3(g), dim3(kBlock), 0, stream, desc, n, g, arena, arena_bytes, eg, l3_port,
                        fwd_status, l2_port, port, ops, queue);
+    return hipGetLastError();
+}
+
+// ---- Ingress dispatch: what process_received_packet does between the stages ----------
+// l2_lookup_kernel's shape: a wave takes 64 packets, one lane each, with route_lookup_kernel's descriptor load
+// and XCD-aware block order; no loop. The decision is nfcs_switch.h sw_classify, the host walk's own function.
+// A frame is read only where the ingress link is up, the frame is permitted, its descriptor lies inside the
+// arena and it has an Ethernet header: bytes 0..15 with one 16-byte load, and bytes 16..19 (the inner EtherType
+// behind a tag, inside the arena once len > 16) with one 4-byte load where len >= 18. Both loads are issued
+// together, before anything uses either (a lane that reads nothing loads the zero line), non-temporal: the
+// frames are streamed. The redirect port's state byte is gathered by the redirecting lanes only.
+// COUNT (d_rx_stats given): packets (one per frame, two per dropped frame) and drops are packed into one
+// word, the bytes are 64-bit; both are summed across the wave by xor shuffles, the four wave sums meet in LDS,
+// and thread 0 adds the workgroup's sums with at most one 64-bit vector atomic per counter.
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) void ingress_dispatch_kernel(const nfcs_desc* __restrict__ desc, uint32_t n,
+                                                                  uint32_t nblocks, const uint8_t* __restrict__ arena,
+                                                                  uint64_t arena_bytes,
+                                                                  const uint8_t* __restrict__ port_state, uint32_t ports,
+                                                                  const DispatchArgs a) {
+    __shared__ unsigned long long s_bytes[kWavesPerBlock];
+    __shared__ uint32_t s_cnt[kWavesPerBlock];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t p0 = ((uint64_t)xcd_block_n(nblocks) * kWavesPerBlock + rfl(wave)) * 64u;
+    if (!COUNT && p0 >= n) return;  // a counting wave past n reaches the barrier with zeros
+    const uint64_t p = p0 + lane;
+    const bool in = p < n;
+    uint2 dl = make_uint2(0u, 0u);
+    uint32_t act = NFCS_ACL_PERMIT, red = NFCS_IF_NONE, rt = NFCS_RT_NOT_IPV4, l2v = NFCS_L2_SKIP;
+    if (in) {
+        dl = ((const uint2*)desc)[p];
+        if (a.action) act = a.action[p];
+        if (a.redirect) red = a.redirect[p];
+        rt = a.rt_verdict[p];
+        l2v = a.l2_verdict[p];
+    }
+    // is_port_link_up(ingress_port_id) (215): uniform over the launch
+    const bool rx_up = a.ingress < ports && (port_state[a.ingress] & kSwLinkUp) != 0;
+    const uint32_t len = dl.y;
+    const uint64_t off = (uint64_t)dl.x * 16u;
+    const bool live = sw_desc_live(dl.x, len, arena_bytes);
+    const bool rd0 = in && rx_up && sw_reads_head(act, rt, live, len);
+    const bool rd1 = in && rx_up && sw_reads_inner(act, rt, live, len);
+    const uint4 c = ld16<1>(rd0 ? (const uint4*)(arena + off) : g_zero_line);
+    const uint32_t w4 =
+        __builtin_nontemporal_load(rd1 ? (const uint32_t*)(arena + off + 16u) : (const uint32_t*)g_zero_line);
+    bool red_up = false;  // is_port_link_up(redirect port) (233)
+    if (in && act == NFCS_ACL_REDIRECT && red < a.num_ports && red < ports) red_up = (port_state[red] & kSwLinkUp) != 0;
+    const uint32_t cls = !rx_up ? (uint32_t)NFCS_SW_RX_DOWN
+                                : sw_classify(len, live, act, red, a.num_ports, red_up, rt, l2v, c.x, c.y, c.w, w4);
+    if (in) {  // one packet per lane: each store instruction writes consecutive elements (predicated)
+        if (sw_masked(cls) || cls == NFCS_SW_RED_OK) {
+            a.nh[p] = NFCS_NH_NONE;
+            a.l2_port[p] = cls == NFCS_SW_RED_OK ? red : NFCS_IF_NONE;
+            a.l2_verdict[p] = (uint8_t)NFCS_L2_SKIP;
+        }
+        if (a.cls) a.cls[p] = (uint8_t)cls;
+        if (a.bypass) a.bypass[p] = (uint8_t)(cls == NFCS_SW_RED_OK);
+    }
+    if (COUNT) {
+        if (!rx_up) return;  // uniform over the launch: nothing is counted (215 returns before 216)
+        const uint32_t drop = (in && sw_drop(cls)) ? 1u : 0u;
+        const uint32_t pk = in ? 1u + drop : 0u;          // 216, and once more at 228 / 235
+        uint32_t cnt = pk | (drop << 16);                 // at most 128 and 64 per wave
+        unsigned long long by = (unsigned long long)len * pk;
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            cnt += (uint32_t)__shfl_xor((int)cnt, m);
+            const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)by, m);
+            const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(by >> 32), m);
+            by += ((unsigned long long)hi << 32) | lo;
+        }
+        if (lane == 0) {
+            s_bytes[wave] = by;
+            s_cnt[wave] = cnt;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t tc = 0;
+            unsigned long long tb = 0;
+#pragma unroll
+            for (int w = 0; w < kWavesPerBlock; ++w) {
+                tc += s_cnt[w];
+                tb += s_bytes[w];
+            }
+            unsigned long long* rx = (unsigned long long*)(a.rx_stats + a.ingress);
+            if (tc & 0xFFFFu) atomicAdd(rx + 0, (unsigned long long)(tc & 0xFFFFu));
+            if (tb) atomicAdd(rx + 1, tb);
+            if (tc >> 16) atomicAdd(rx + 2, (unsigned long long)(tc >> 16));
+        }
+    }
+}
+
+hipError_t launch_ingress_dispatch(const DevInfo& di, const FdbDev& fdb, const DispatchArgs& a, hipStream_t stream) {
+    (void)di;
+    if (a.n == 0) return hipSuccess;
+    const uint32_t g = (a.n + 255u) / 256u;
+    if (a.rx_stats)
+        hipLaunchKernelGGL(ingress_dispatch_kernel<true>, dim3(g), dim3(kBlock), 0, stream, a.desc, a.n, g, a.arena,
+                           a.arena_bytes, fdb.port_state, fdb.ports, a);
+    else
+        hipLaunchKernelGGL(ingress_dispatch_kernel<false>, dim3(g), dim3(kBlock), 0, stream, a.desc, a.n, g, a.arena,
+                           a.arena_bytes, fdb.port_state, fdb.ports, a);
     return hipGetLastError();
 }
 
@@ -3943,7 +4056,7 @@ __global__ __launch_bounds__(kBlock) void txq_append_kernel(const TxqDev t, cons
                                                             const uint32_t* __restrict__ depth,
                                                             const uint64_t* __restrict__ handle,
                                                             const nfcs_desc* __restrict__ desc, uint32_t n,
-                                                            uint32_t trips) {
+                                                            uint32_t trips, uint64_t handle_base) {
     const uint64_t j64 = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (j64 >= n) return;
     const uint32_t j = (uint32_t)j64, keys = t.keys;
@@ -3965,19 +4078,22 @@ __global__ __launch_bounds__(kBlock) void txq_append_kernel(const TxqDev t, cons
     uint64_t h;
     if (handle) {
         h = handle[i];
-    } else {
+    } else if (desc) {
         const uint2 dl = ((const uint2*)desc)[i];
         h = txq_desc_handle(dl.x, dl.y);
+    } else {
+        h = handle_base + i;
     }
     t.ring[slot] = h;
 }
 
 hipError_t launch_txq_append(const TxqDev& t, const uint32_t* order, const uint32_t* key_start, const uint32_t* depth,
-                             const uint64_t* handle, const nfcs_desc* desc, uint32_t n, hipStream_t stream) {
+                             const uint64_t* handle, const nfcs_desc* desc, uint32_t n, hipStream_t stream,
+                             uint64_t handle_base) {
     if (n == 0 || t.keys == 0) return hipSuccess;
     const uint32_t trips = 32u - (uint32_t)__builtin_clz(t.keys + 1u);
     hipLaunchKernelGGL(txq_append_kernel, dim3((n + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, t, order, key_start,
-                       depth, handle, desc, n, trips);
+                       depth, handle, desc, n, trips, handle_base);
     return hipGetLastError();
 }
 
