@@ -1998,6 +1998,90 @@ hipError_t launch_vlan(const DevInfo& di, uint8_t* arena, uint64_t arena_bytes, 
     return hipGetLastError();
 }
 
+// ---- the lane-per-packet stage shape -------------------------------------------
+// What the read-only stage kernels below share: a wave takes 64 consecutive packets in XCD-aware block
+// order and lane l decides packet l. A kernel states its own decision and calls these for the rest.
+inline uint32_t lane_blocks(uint32_t n) { return (n + 255u) / 256u; }  // kBlock lanes, one packet each
+
+// Lane l's packet. d is zero past n; a dead packet (past n, or with a chunk outside the arena) reads as
+// length 0, so nothing of its frame is requested. A kernel's further conditions are `&&` on live, and
+// where a wave past n returns (before a barrier, after it, or not at all) is the kernel's choice.
+struct LanePkt {
+    uint64_t p0, p;  // the wave's first packet, this lane's packet
+    uint2 d;         // the descriptor {off16, len}
+    uint64_t off;    // the frame's byte offset in the arena
+    bool live;
+    uint32_t len;
+};
+DEV LanePkt lane_pkt(const nfcs_desc* __restrict__ desc, uint32_t n, uint32_t nblocks, uint64_t arena_bytes) {
+    LanePkt k;
+    k.p0 = ((uint64_t)xcd_block_n(nblocks) * kWavesPerBlock + rfl(threadIdx.x >> 6)) * 64u;
+    k.p = k.p0 + (threadIdx.x & 63u);
+    k.d = make_uint2(0u, 0u);
+    if (k.p < n) k.d = ((const uint2*)desc)[k.p];  // one coalesced load
+    k.off = (uint64_t)k.d.x * 16u;
+    k.live = k.p < n && sw_desc_live(k.d.x, k.d.y, arena_bytes);
+    k.len = k.live ? k.d.y : 0u;
+    return k;
+}
+
+// Header chunks 0..2 (bytes 0..47) of the wave's 64 packets in 8-lane rows: instruction k, row r ->
+// packet 8k + r, lane rl -> chunk rl, so one instruction reads one line of each of 8 packets and 8 are in
+// flight. off16 / len are the lane's own packet's; chunks at or past len read the zero line. Non-temporal:
+// the frames are read once. The loads stay in flight until hdr_rows_store, so a kernel that stages a table
+// issues them first and stores the rows after its barrier.
+DEV void hdr_rows_load(const uint8_t* __restrict__ arena, uint32_t off16, uint32_t len, uint32_t lane, uint4 (&c)[8]) {
+    const uint32_t rl = lane & 7u, r = lane >> 3;
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) {
+        const uint32_t q = 8u * k + r;
+        const uint32_t qo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)off16);
+        const uint32_t ql = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)len);
+        const uint4* src = (const uint4*)(arena + (uint64_t)qo * 16u);
+        c[k] = ld16<1>((rl < 3u && rl * 16u < ql) ? src + rl : g_zero_line);
+    }
+}
+// The rows into the wave's LDS, ROW bytes per packet; on return every lane may read its packet's row.
+template <uint32_t ROW>
+DEV void hdr_rows_store(uint8_t* rows, uint32_t lane, const uint4 (&c)[8]) {
+    const uint32_t rl = lane & 7u, r = lane >> 3;
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k)
+        if (rl < 3u) *(uint4*)(rows + (8u * k + r) * ROW + 16u * rl) = c[k];
+    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes are done
+    __builtin_amdgcn_wave_barrier();
+}
+// Headers past byte 47 (IPv6, IPv4 options): the lanes with `more` load chunks 3..5 of their own frame
+// into their row b (96 bytes). Every lane of the wave calls it.
+DEV void hdr_late_chunks(uint8_t* b, const uint8_t* __restrict__ arena, uint64_t off, uint32_t len, bool more) {
+    if (__builtin_amdgcn_ballot_w64(more) == 0) return;
+    if (more) {
+        const uint4* src = (const uint4*)(arena + off);
+#pragma unroll
+        for (uint32_t j = 3; j < 6; ++j) *(uint4*)(b + 16u * j) = ld16<0>(16u * j < len ? src + j : g_zero_line);
+    }
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier();
+}
+
+// A table of n4 16-byte pieces into LDS, once per workgroup: every thread takes part and the caller's
+// __syncthreads() follows. Four loads in flight per lane (the index clamped, not branched).
+DEV void stage_to_lds(uint4* dst, const uint4* src, uint32_t n4) {
+    for (uint32_t i0 = 0; i0 < n4; i0 += 4u * kBlock) {
+        uint4 t[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t i = i0 + j * kBlock + threadIdx.x;
+            t[j] = src[i < n4 ? i : n4 - 1u];
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t i = i0 + j * kBlock + threadIdx.x;
+            if (i < n4) dst[i] = t[j];
+        }
+    }
+}
+
 // ---- flow-key extract + hash -----------------------------------------------
 // PacketClassifier::extract_flow_key + hash_flow (packet_classifier.cpp:12-108) on the first 96
 // bytes of each frame (every field the key reads lies below byte 82: l2 18 + IHL 60 + 4 port bytes).
@@ -2026,39 +2110,21 @@ __global__ __launch_bounds__(kBlock) void flow_keys_lanes_kernel(const nfcs_desc
                                                                  uint32_t* __restrict__ hashes) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock * 64 * kFkRow];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t p0 = ((uint64_t)xcd_block_n(nblocks) * kWavesPerBlock + rfl(wave)) * 64u;
+    const LanePkt lp = lane_pkt(desc, n, nblocks, arena_bytes);
+    const uint64_t p0 = lp.p0, p = lp.p;
     if (p0 >= n) return;
     uint8_t* rows = lds + wave * 64u * kFkRow;
-    // lane l: descriptor of packet p0 + l (one coalesced load); dead packets read as length 0
-    const uint64_t p = p0 + lane;
-    uint2 dl = make_uint2(0u, 0u);
-    if (p < n) dl = ((const uint2*)desc)[p];
-    const uint64_t off = (uint64_t)dl.x * 16u;
-    const bool live = p < n && off + (((uint64_t)dl.y + 15u) & ~15ull) <= arena_bytes;
-    const uint32_t len = live ? dl.y : 0u;
-    // Header bytes 0..47 (every field of an IPv4 header without options, tagged or not, and its
-    // ports) in 8-lane rows: instruction k, row r -> packet 8k + r, lane rl -> chunk rl (0..2). A
-    // frame starting up to 80 bytes into a 128-byte line reads that one line (64-byte starts: one
-    // line instead of two; round 3). Headers reaching past byte 47 (IPv6, IPv4 options) load chunks
+    const bool live = lp.live;
+    const uint32_t len = lp.len;
+    // Header bytes 0..47 hold every field of an IPv4 header without options, tagged or not, and its
+    // ports. A frame starting up to 80 bytes into a 128-byte line reads that one line (64-byte starts:
+    // one line instead of two; round 3). Headers reaching past byte 47 (IPv6, IPv4 options) load chunks
     // 3..5 afterwards, lane by lane. The header lines load non-temporally (round 5, calls rotating
     // over fresh batches, same box: 0.0385-0.0390 against 0.0411-0.0414 ms per 1M C1 frames; `sc1` /
     // `sc0 sc1` loads measured as the default; profiles/r05_flowkey_load_policy_ab.jsonl).
-    const uint32_t rl = lane & 7u, r = lane >> 3;
-    const uint4* zl = g_zero_line;
     uint4 c[8];
-#pragma unroll
-    for (uint32_t k = 0; k < 8; ++k) {
-        const uint32_t q = 8u * k + r;
-        const uint32_t qo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)dl.x);
-        const uint32_t ql = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)len);
-        const uint4* src = (const uint4*)(arena + (uint64_t)qo * 16u);
-        c[k] = ld16<1>((rl < 3u && rl * 16u < ql) ? src + rl : zl);
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < 8; ++k)
-        if (rl < 3u) *(uint4*)(rows + (8u * k + r) * kFkRow + 16u * rl) = c[k];
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes are done
-    __builtin_amdgcn_wave_barrier();
+    hdr_rows_load(arena, lp.d.x, len, lane, c);
+    hdr_rows_store<kFkRow>(rows, lane, c);
     // lane l parses packet l (extract_flow_key + hash_flow, packet_classifier.cpp:12-108)
     uint8_t* b = rows + lane * kFkRow;
     {  // the bytes the key reads end at the ports (IPv4: l2 + IHL*4 + 4; IPv6: l2 + 44)
@@ -2066,16 +2132,7 @@ __global__ __launch_bounds__(kBlock) void flow_keys_lanes_kernel(const nfcs_desc
         const uint32_t fet = (f12 == 0x8100u && len >= 18) ? lds_be16(b, 16) : f12;
         const uint32_t need = (fet == 0x0800u && 34u + ft <= len) ? 18u + ft + (lds_u8(b, 14u + ft) & 15u) * 4u
                             : (fet == 0x86DDu && 54u + ft <= len) ? 58u + ft : 0u;
-        const bool more = len >= 14 && need > 48u && len > 48u;
-        if (__builtin_amdgcn_ballot_w64(more) != 0) {
-            if (more) {
-                const uint4* src = (const uint4*)(arena + off);
-#pragma unroll
-                for (uint32_t j = 3; j < 6; ++j) *(uint4*)(b + 16u * j) = ld16<0>(16u * j < len ? src + j : zl);
-            }
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_wave_barrier();
-        }
+        hdr_late_chunks(b, arena, lp.off, len, len >= 14 && need > 48u && len > 48u);
     }
     const bool eth = len >= 14;
     const uint32_t m0 = eth ? *(const uint32_t*)b : 0u, m1 = eth ? *(const uint32_t*)(b + 4) : 0u;
@@ -2149,17 +2206,17 @@ hipError_t launch_flow_keys(const DevInfo& di, const uint8_t* arena, uint64_t ar
     if (n == 0) return hipSuccess;
     // 64 packets per wave, one lane each (round 3: C1 0.77 -> 0.82 against round 2's 8-lane rows of
     // 4 slots; profiles/r03_s2_ab_flowkey_lanes.jsonl); write-back record stores, XCD-aware order
-    const uint32_t g = (n + 255u) / 256u;
+    const uint32_t g = lane_blocks(n);
     hipLaunchKernelGGL(flow_keys_lanes_kernel, dim3(g), dim3(kBlock), 0, stream, desc, n, g, arena, arena_bytes, keys,
                        hashes);
     return hipGetLastError();
 }
 
 // ---- route + ARP lookup in front of the fused forward -------------------------
-// The switch's L3 decision (switch.hpp:259-301) per packet, in flow_keys_lanes_kernel's shape: a wave
-// takes 64 packets, loads header bytes 0..47 (every byte the decision reads lies below 38) in 8-lane
-// rows, one line per packet, and lane l decides packet l from LDS. The {network, mask} pairs of the
-// routes are staged once per workgroup in LDS behind the header rows and scanned in lookup order by
+// The switch's L3 decision (switch.hpp:259-301) per packet: lane_pkt, header bytes 0..47 (every byte the
+// decision reads lies below 38) by hdr_rows_load / hdr_rows_store, and lane l decides packet l from LDS. The
+// {network, mask} pairs of the routes are staged once per workgroup in LDS behind the header rows
+// (stage_to_lds, issued between the rows' loads and their store) and scanned in lookup order by
 // a wave-uniform loop: every lane reads the same pair (an LDS broadcast, no bank conflict), kRtGroup
 // pairs per trip, and the wave leaves the loop once each of its lanes has its first match
 // (RoutingManager::lookup_route, routing_manager.cpp:80-92). ARP entries and the switch's own
@@ -2185,54 +2242,19 @@ __global__ __launch_bounds__(kBlock) void route_lookup_kernel(const nfcs_desc* _
                                                               uint8_t* __restrict__ verdict_out) {
     extern __shared__ __attribute__((aligned(16))) uint8_t rt_lds[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t p0 = ((uint64_t)xcd_block_n(nblocks) * kWavesPerBlock + rfl(wave)) * 64u;
+    const LanePkt lp = lane_pkt(desc, n, nblocks, arena_bytes);
+    const uint64_t p0 = lp.p0, p = lp.p;
     uint8_t* rows = rt_lds + wave * 64u * kRtRow;
-    // lane l: descriptor of packet p0 + l (one coalesced load); dead packets read as length 0
-    const uint64_t p = p0 + lane;
-    uint2 dl = make_uint2(0u, 0u);
-    if (p < n) dl = ((const uint2*)desc)[p];
-    const uint64_t off = (uint64_t)dl.x * 16u;
-    const bool live = p < n && off + (((uint64_t)dl.y + 15u) & ~15ull) <= arena_bytes;
-    const uint32_t len = live ? dl.y : 0u;
-    // header chunks 0..2 in 8-lane rows (instruction k, row r -> packet 8k + r, lane rl -> chunk rl),
-    // non-temporal: the frames are read once
-    const uint32_t rl = lane & 7u, r = lane >> 3;
-    const uint4* zl = g_zero_line;
+    const bool live = lp.live;
+    const uint32_t len = lp.len;
     uint4 c[8];
-    if (p0 < n) {
-#pragma unroll
-        for (uint32_t k = 0; k < 8; ++k) {
-            const uint32_t q = 8u * k + r;
-            const uint32_t qo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)dl.x);
-            const uint32_t ql = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)len);
-            const uint4* src = (const uint4*)(arena + (uint64_t)qo * 16u);
-            c[k] = ld16<1>((rl < 3u && rl * 16u < ql) ? src + rl : zl);
-        }
-    }
+    if (p0 < n) hdr_rows_load(arena, lp.d.x, len, lane, c);
     // the routes' {network, mask} pairs, two per 16-byte piece, once per workgroup (every wave of the
     // workgroup takes part, also one past n: it leaves after the barrier)
-    uint4* rt4 = (uint4*)(rt_lds + kRtRowsBytes);
-    const uint32_t n4 = fib.routes_padded / 2u;
-    for (uint32_t i0 = 0; i0 < n4; i0 += 4u * kBlock) {  // 4 loads in flight per lane (index clamped, not branched)
-        uint4 t[4];
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-            const uint32_t i = i0 + j * kBlock + threadIdx.x;
-            t[j] = ((const uint4*)fib.rt_nm)[i < n4 ? i : n4 - 1u];
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-            const uint32_t i = i0 + j * kBlock + threadIdx.x;
-            if (i < n4) rt4[i] = t[j];
-        }
-    }
+    stage_to_lds((uint4*)(rt_lds + kRtRowsBytes), (const uint4*)fib.rt_nm, fib.routes_padded / 2u);
     __syncthreads();
     if (p0 >= n) return;
-#pragma unroll
-    for (uint32_t k = 0; k < 8; ++k)
-        if (rl < 3u) *(uint4*)(rows + (8u * k + r) * kRtRow + 16u * rl) = c[k];
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes are done
-    __builtin_amdgcn_wave_barrier();
+    hdr_rows_store<kRtRow>(rows, lane, c);
     // lane l decides packet l. The forward's predicate (row_process above): L3 EtherType after at
     // most one tag, ipv4() present
     const uint8_t* b = rows + lane * kRtRow;
@@ -2283,7 +2305,7 @@ hipError_t launch_route_lookup(const DevInfo& di, const FibDev& fib, const uint8
     (void)di;
     if (n == 0) return hipSuccess;
     // 64 packets per wave, one lane each, XCD-aware order; LDS: the header rows, then the pairs
-    const uint32_t g = (n + 255u) / 256u;
+    const uint32_t g = lane_blocks(n);
     const unsigned lds = kRtRowsBytes + fib.routes_padded * 8u;
     hipLaunchKernelGGL(route_lookup_kernel, dim3(g), dim3(kBlock), lds, stream, desc, n, g, arena, arena_bytes, fib,
                        nh, egress_if, verdict);
@@ -2291,79 +2313,23 @@ hipError_t launch_route_lookup(const DevInfo& di, const FibDev& fib, const uint8
 }
 
 // ---- ACL evaluation in front of the lookup and the forward --------------------
-// AclManager::evaluate (acl_manager.cpp:161-278) per packet, in flow_keys_lanes_kernel's shape: a wave
-// takes 64 packets, loads header bytes 0..47 in 8-lane rows, one line per packet, lane l reads packet l
-// from LDS (96 bytes per packet; headers whose ports lie past byte 47 — IPv4 options — load chunks 3..5
-// afterwards, lane by lane) and folds every field check_match can read into a key of eight dwords
-// (nfcs_acl.h acl_key). The compiled rules {value[8], mask[8]} are staged once per workgroup in LDS
-// behind the header rows and scanned in the given order by a wave-uniform loop: every lane reads the
-// same rule (LDS broadcasts), kAclGroup rules per trip folded last to first so the first in order wins,
-// one ballot per trip, and the wave leaves the loop once each of its live lanes has its match. A trip
-// reads the rules' address / port / protocol halves first and their MAC / VLAN / EtherType halves only
-// when one of its rules tests those (half the LDS traffic for a list of address and port rules).
+// AclManager::evaluate (acl_manager.cpp:161-278) per packet: lane_pkt, header bytes 0..47 by hdr_rows_load /
+// hdr_rows_store (96 bytes of LDS per packet; headers whose ports lie past byte 47 — IPv4 options — take
+// hdr_late_chunks), and lane l folds every field check_match can read into a key of eight dwords
+// (acl_key_lds). The compiled rules {value[8], mask[8]} are staged once per workgroup in LDS behind the
+// header rows (stage_to_lds) and scanned in the given order by a wave-uniform loop of acl_scan_trip:
+// kAclGroup rules per trip folded last to first so the first in order wins, one ballot per trip, and the
+// wave leaves the loop once each of its live lanes has its match. A trip reads the rules' address / port /
+// protocol halves first and their MAC / VLAN / EtherType halves only when one of its rules tests those
+// (half the LDS traffic for a list of address and port rules).
 constexpr uint32_t kAclRowsBytes = kWavesPerBlock * 64u * kFkRow;
 static_assert(kAclRowsBytes + NFCS_ACL_MAX_RULES * sizeof(AclRec) < 64u * 1024u,
               "header rows + rules stay under 64 KiB of dynamic LDS (no opt-in needed)");
 
-__global__ __launch_bounds__(kBlock) void acl_eval_kernel(const nfcs_desc* __restrict__ desc, uint32_t n,
-                                                          uint32_t nblocks, const uint8_t* __restrict__ arena,
-                                                          uint64_t arena_bytes, const AclDev acl,
-                                                          uint8_t* __restrict__ action_out,
-                                                          uint32_t* __restrict__ rule_out,
-                                                          uint32_t* __restrict__ redirect_out,
-                                                          uint32_t* __restrict__ nh_out) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t acl_lds[];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t p0 = ((uint64_t)xcd_block_n(nblocks) * kWavesPerBlock + rfl(wave)) * 64u;
-    uint8_t* rows = acl_lds + wave * 64u * kFkRow;
-    // lane l: descriptor of packet p0 + l (one coalesced load); dead packets read as length 0
-    const uint64_t p = p0 + lane;
-    uint2 dl = make_uint2(0u, 0u);
-    if (p < n) dl = ((const uint2*)desc)[p];
-    const uint64_t off = (uint64_t)dl.x * 16u;
-    const bool live = p < n && off + (((uint64_t)dl.y + 15u) & ~15ull) <= arena_bytes;
-    const uint32_t len = live ? dl.y : 0u;
-    // header chunks 0..2 in 8-lane rows (instruction k, row r -> packet 8k + r, lane rl -> chunk rl),
-    // non-temporal: the frames are read once
-    const uint32_t rl = lane & 7u, r = lane >> 3;
-    const uint4* zl = g_zero_line;
-    uint4 c[8];
-    if (p0 < n) {
-#pragma unroll
-        for (uint32_t k = 0; k < 8; ++k) {
-            const uint32_t q = 8u * k + r;
-            const uint32_t qo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)dl.x);
-            const uint32_t ql = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)len);
-            const uint4* src = (const uint4*)(arena + (uint64_t)qo * 16u);
-            c[k] = ld16<1>((rl < 3u && rl * 16u < ql) ? src + rl : zl);
-        }
-    }
-    // the compiled rules, four 16-byte pieces each, once per workgroup (every wave of the workgroup
-    // takes part, also one past n: it leaves after the barrier)
-    uint4* rec4 = (uint4*)(acl_lds + kAclRowsBytes);
-    const uint32_t n4 = acl.rules_padded * 4u;
-    for (uint32_t i0 = 0; i0 < n4; i0 += 4u * kBlock) {  // 4 loads in flight per lane (index clamped, not branched)
-        uint4 t[4];
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-            const uint32_t i = i0 + j * kBlock + threadIdx.x;
-            t[j] = acl.rec[i < n4 ? i : n4 - 1u];
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-            const uint32_t i = i0 + j * kBlock + threadIdx.x;
-            if (i < n4) rec4[i] = t[j];
-        }
-    }
-    __syncthreads();
-    if (p0 >= n) return;
-#pragma unroll
-    for (uint32_t k = 0; k < 8; ++k)
-        if (rl < 3u) *(uint4*)(rows + (8u * k + r) * kFkRow + 16u * rl) = c[k];
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes are done
-    __builtin_amdgcn_wave_barrier();
-    // lane l builds the key of packet l (nfcs_acl.h acl_key, the same bounds)
-    uint8_t* b = rows + lane * kFkRow;
+// Lane l's key from its packet's LDS row b (kFkRow bytes, chunks 0..2 present): nfcs_acl.h acl_key with the
+// same bounds, read in 2-byte pieces. Loads the late chunks where the ports need them, so every lane of the
+// wave calls it; len is 0 for a packet that is not read.
+DEV void acl_key_lds(uint8_t* b, const uint8_t* __restrict__ arena, uint64_t off, uint32_t len, uint32_t (&key)[8]) {
     const uint32_t e12 = lds_be16(b, 12);
     const bool eth = len >= 14, tagged = e12 == 0x8100u;
     const uint32_t sh = tagged ? 4u : 0u;  // l2 = 18 behind a tag
@@ -2371,19 +2337,8 @@ __global__ __launch_bounds__(kBlock) void acl_eval_kernel(const nfcs_desc* __res
     const uint32_t et = !known ? 0u : tagged ? lds_be16(b, 16) : e12;
     const bool v4 = known && et == 0x0800u && 34u + sh <= len;  // ipv4() present
     const uint32_t l4 = 14u + sh + (lds_u8(b, 14u + sh) & 15u) * 4u;
-    {  // the ports end at l4 + 4: past byte 47 only with IPv4 options (IHL >= 8; 7 behind a tag)
-        const bool more = v4 && l4 + 4u > 48u && len > 48u;
-        if (__builtin_amdgcn_ballot_w64(more) != 0) {
-            if (more) {
-                const uint4* src = (const uint4*)(arena + off);
-#pragma unroll
-                for (uint32_t j = 3; j < 6; ++j) *(uint4*)(b + 16u * j) = ld16<0>(16u * j < len ? src + j : zl);
-            }
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-    uint32_t key[8];
+    // the ports end at l4 + 4: past byte 47 only with IPv4 options (IHL >= 8; 7 behind a tag)
+    hdr_late_chunks(b, arena, off, len, v4 && l4 + 4u > 48u && len > 48u);
     key[kAkMac0] = eth ? *(const uint32_t*)b : 0u;
     key[kAkMac1] = eth ? *(const uint32_t*)(b + 4) : 0u;
     key[kAkMac2] = eth ? *(const uint32_t*)(b + 8) : 0u;
@@ -2406,39 +2361,70 @@ __global__ __launch_bounds__(kBlock) void acl_eval_kernel(const nfcs_desc* __res
     key[kAkDstIp] = dip;
     key[kAkPorts] = ports;
     key[kAkMeta] = meta;
-    // the scan: rule i + j matches when ((key ^ value) & mask) == 0 over the eight dwords
+}
+
+// One trip of the scan over rules i .. i + kAclGroup - 1 of rec (LDS; the same rules for every lane, so the
+// reads are broadcasts and the branch is uniform): the first of them in order that the key matches —
+// ((key ^ value) & mask) == 0 over the eight dwords — or NFCS_ACL_NO_MATCH. Dwords 4..7 (addresses, ports,
+// protocol and presence bits) of the trip's rules first; dwords 0..3 (MACs, VLAN id, EtherType) only when
+// one of these rules tests them, which its mask says in a bit no key has (kApNeedL2).
+DEV uint32_t acl_scan_trip(const uint4* rec, uint32_t i, const uint32_t (&key)[8]) {
+    uint32_t d[kAclGroup], l2 = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kAclGroup; ++j) {
+        const uint4* e = rec + (i + j) * 4u;
+        const uint4 v1 = e[1], m1 = e[3];
+        d[j] = (key[4] ^ v1.x) & m1.x;
+        d[j] |= (key[5] ^ v1.y) & m1.y;
+        d[j] |= (key[6] ^ v1.z) & m1.z;
+        d[j] |= (key[7] ^ v1.w) & m1.w;
+        l2 |= m1.w;
+    }
+    if (rfl(l2) & kApNeedL2) {
+#pragma unroll
+        for (uint32_t j = 0; j < kAclGroup; ++j) {
+            const uint4* e = rec + (i + j) * 4u;
+            const uint4 v0 = e[0], m0 = e[2];
+            d[j] |= (key[0] ^ v0.x) & m0.x;
+            d[j] |= (key[1] ^ v0.y) & m0.y;
+            d[j] |= (key[2] ^ v0.z) & m0.z;
+            d[j] |= (key[3] ^ v0.w) & m0.w;
+        }
+    }
+    uint32_t m = NFCS_ACL_NO_MATCH;
+#pragma unroll
+    for (uint32_t j = kAclGroup; j-- > 0;) m = d[j] == 0 ? i + j : m;  // descending: the first rule in order wins
+    return m;
+}
+
+__global__ __launch_bounds__(kBlock) void acl_eval_kernel(const nfcs_desc* __restrict__ desc, uint32_t n,
+                                                          uint32_t nblocks, const uint8_t* __restrict__ arena,
+                                                          uint64_t arena_bytes, const AclDev acl,
+                                                          uint8_t* __restrict__ action_out,
+                                                          uint32_t* __restrict__ rule_out,
+                                                          uint32_t* __restrict__ redirect_out,
+                                                          uint32_t* __restrict__ nh_out) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t acl_lds[];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const LanePkt lp = lane_pkt(desc, n, nblocks, arena_bytes);
+    const uint64_t p0 = lp.p0, p = lp.p;
+    uint8_t* rows = acl_lds + wave * 64u * kFkRow;
+    const bool live = lp.live;
+    uint4 c[8];
+    if (p0 < n) hdr_rows_load(arena, lp.d.x, lp.len, lane, c);
+    // the compiled rules, four 16-byte pieces each, once per workgroup (every wave of the workgroup
+    // takes part, also one past n: it leaves after the barrier)
+    stage_to_lds((uint4*)(acl_lds + kAclRowsBytes), acl.rec, acl.rules_padded * 4u);
+    __syncthreads();
+    if (p0 >= n) return;
+    hdr_rows_store<kFkRow>(rows, lane, c);
+    uint32_t key[8];
+    acl_key_lds(rows + lane * kFkRow, arena, lp.off, lp.len, key);
     const uint4* rec = (const uint4*)(acl_lds + kAclRowsBytes);
     uint32_t match = NFCS_ACL_NO_MATCH;
     for (uint32_t i = 0; i < acl.rules_padded; i += kAclGroup) {
         if (__builtin_amdgcn_ballot_w64(live && match == NFCS_ACL_NO_MATCH) == 0) break;
-        // dwords 4..7 (addresses, ports, protocol and presence bits) of the trip's rules first; dwords 0..3
-        // (MACs, VLAN id, EtherType) only when one of these rules tests them, which its mask says in a
-        // bit no key has (kApNeedL2). The rules are the same for every lane, so the branch is uniform.
-        uint32_t d[kAclGroup], l2 = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kAclGroup; ++j) {
-            const uint4* e = rec + (i + j) * 4u;
-            const uint4 v1 = e[1], m1 = e[3];
-            d[j] = (key[4] ^ v1.x) & m1.x;
-            d[j] |= (key[5] ^ v1.y) & m1.y;
-            d[j] |= (key[6] ^ v1.z) & m1.z;
-            d[j] |= (key[7] ^ v1.w) & m1.w;
-            l2 |= m1.w;
-        }
-        if (rfl(l2) & kApNeedL2) {
-#pragma unroll
-            for (uint32_t j = 0; j < kAclGroup; ++j) {
-                const uint4* e = rec + (i + j) * 4u;
-                const uint4 v0 = e[0], m0 = e[2];
-                d[j] |= (key[0] ^ v0.x) & m0.x;
-                d[j] |= (key[1] ^ v0.y) & m0.y;
-                d[j] |= (key[2] ^ v0.z) & m0.z;
-                d[j] |= (key[3] ^ v0.w) & m0.w;
-            }
-        }
-        uint32_t m = NFCS_ACL_NO_MATCH;
-#pragma unroll
-        for (uint32_t j = kAclGroup; j-- > 0;) m = d[j] == 0 ? i + j : m;  // descending: the first rule in order wins
+        const uint32_t m = acl_scan_trip(rec, i, key);
         match = match == NFCS_ACL_NO_MATCH ? m : match;
     }
     uint32_t action = live ? NFCS_ACL_PERMIT : NFCS_ACL_BAD_DESC, redirect = NFCS_IF_NONE;
@@ -2462,7 +2448,7 @@ hipError_t launch_acl_eval(const DevInfo& di, const AclDev& acl, const uint8_t* 
     (void)di;
     if (n == 0) return hipSuccess;
     // 64 packets per wave, one lane each, XCD-aware order; LDS: the header rows, then the rules
-    const uint32_t g = (n + 255u) / 256u;
+    const uint32_t g = lane_blocks(n);
     const unsigned lds = kAclRowsBytes + acl.rules_padded * (unsigned)sizeof(AclRec);
     hipLaunchKernelGGL(acl_eval_kernel, dim3(g), dim3(kBlock), lds, stream, desc, n, g, arena, arena_bytes, acl, action,
                        rule, redirect, nh);
@@ -2470,13 +2456,13 @@ hipError_t launch_acl_eval(const DevInfo& di, const AclDev& acl, const uint8_t* 
 }
 
 // ---- Egress ACLs: the list chosen per packet by its egress port -----------------
-// acl_eval_kernel's shape (64 packets per wave, one lane each; header chunks 0..2 in 8-lane rows; the late
-// chunks; every rule staged once per workgroup behind the header rows), with the rule list taken from the
-// packet's egress port: lane l gathers its port's binding {first rule, padded count} (the binding array is
+// The ACL stage's functions (lane_pkt; hdr_rows_load / hdr_rows_store; acl_key_lds; every rule staged once
+// per workgroup behind the header rows by stage_to_lds), with the rule list taken from the packet's egress
+// port: lane l gathers its port's binding {first rule, padded count} (the binding array is
 // small and reused: default cache policy). A lane whose packet needs no scan — no port, a descriptor
 // outside the arena, a port without a list — requests no frame bytes (its row loads read the zero line), and
 // a wave without any scan skips rows, keys and scan. The scan is a waterfall over the lists present in the
-// wave: take the binding of the first pending lane (readfirstlane), run acl_eval_kernel's wave-uniform scan
+// wave: take the binding of the first pending lane (readfirstlane), run the wave-uniform scan (acl_scan_trip)
 // over that list's range for the lanes bound to it, retire them, repeat. Every list is scanned at most once
 // per wave, and a wave whose packets all leave by one port runs exactly the single-list loop.
 // Deny counters: the denied lanes of a wave are grouped by port (the same waterfall), each group's lengths
@@ -2498,16 +2484,13 @@ __global__ __launch_bounds__(kBlock) void egress_acl_kernel(const nfcs_desc* __r
                                                             const uint8_t* __restrict__ bypass, uint32_t n_src) {
     extern __shared__ __attribute__((aligned(16))) uint8_t ea_lds[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t p0 = ((uint64_t)xcd_block_n(nblocks) * kWavesPerBlock + rfl(wave)) * 64u;
+    const LanePkt lp = lane_pkt(desc, n, nblocks, arena_bytes);
+    const uint64_t p0 = lp.p0, p = lp.p;
+    const uint2 dl = lp.d;
     uint8_t* rows = ea_lds + wave * 64u * kFkRow;
-    // lane l: port and descriptor of packet p0 + l (coalesced loads), then its port's binding
-    const uint64_t p = p0 + lane;
-    uint2 dl = make_uint2(0u, 0u);
+    // lane l: the port of packet p0 + l (a coalesced load), then its port's binding
     uint32_t port = NFCS_IF_NONE;
-    if (p < n) {
-        dl = ((const uint2*)desc)[p];
-        port = port_io[p];
-    }
+    if (p < n) port = port_io[p];
     const bool has_port = port != NFCS_IF_NONE;  // false past n; without a port the descriptor means nothing
     // an item of a redirected frame bypasses the ACL (switch.hpp:238-240): it keeps its port unread and uncounted
     bool byp = false;
@@ -2515,98 +2498,24 @@ __global__ __launch_bounds__(kBlock) void egress_acl_kernel(const nfcs_desc* __r
         const uint32_t src = item_src[p];
         if (src < n_src) byp = bypass[src] != 0;
     }
-    const uint64_t off = (uint64_t)dl.x * 16u;
-    const bool live = has_port && !byp && off + (((uint64_t)dl.y + 15u) & ~15ull) <= arena_bytes;
+    const bool live = lp.live && has_port && !byp;
     uint2 bind = make_uint2(0u, 0u);
     if (live && port < set.ports) bind = set.bind[port];
     const bool scan = bind.y != 0u;  // the frame is read only for these
     const uint32_t len = scan ? dl.y : 0u;
     const bool any = __builtin_amdgcn_ballot_w64(scan) != 0;  // wave-uniform
-    // header chunks 0..2 in 8-lane rows (instruction k, row r -> packet 8k + r, lane rl -> chunk rl),
-    // non-temporal: the frames are read once
-    const uint32_t rl = lane & 7u, r = lane >> 3;
-    const uint4* zl = g_zero_line;
     uint4 c[8];
-    if (any) {
-#pragma unroll
-        for (uint32_t k = 0; k < 8; ++k) {
-            const uint32_t q = 8u * k + r;
-            const uint32_t qo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)dl.x);
-            const uint32_t ql = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)len);
-            const uint4* src = (const uint4*)(arena + (uint64_t)qo * 16u);
-            c[k] = ld16<1>((rl < 3u && rl * 16u < ql) ? src + rl : zl);
-        }
-    }
+    if (any) hdr_rows_load(arena, dl.x, len, lane, c);
     // every list's compiled rules, four 16-byte pieces each, once per workgroup (every wave of the
     // workgroup takes part, also one past n or without a scan: it reaches the barrier)
-    uint4* rec4 = (uint4*)(ea_lds + kAclRowsBytes + kEaSlotsBytes);
-    const uint32_t n4 = set.rules_padded * 4u;
-    for (uint32_t i0 = 0; i0 < n4; i0 += 4u * kBlock) {  // 4 loads in flight per lane (index clamped, not branched)
-        uint4 t[4];
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-            const uint32_t i = i0 + j * kBlock + threadIdx.x;
-            t[j] = set.rec[i < n4 ? i : n4 - 1u];
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-            const uint32_t i = i0 + j * kBlock + threadIdx.x;
-            if (i < n4) rec4[i] = t[j];
-        }
-    }
+    stage_to_lds((uint4*)(ea_lds + kAclRowsBytes + kEaSlotsBytes), set.rec, set.rules_padded * 4u);
     __syncthreads();
     if (p0 >= n) return;
     uint32_t match = NFCS_ACL_NO_MATCH;  // an index into the one array
     if (any) {
-#pragma unroll
-        for (uint32_t k = 0; k < 8; ++k)
-            if (rl < 3u) *(uint4*)(rows + (8u * k + r) * kFkRow + 16u * rl) = c[k];
-        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes are done
-        __builtin_amdgcn_wave_barrier();
-        // lane l builds the key of packet l (nfcs_acl.h acl_key, the same bounds); len is 0 without a scan
-        uint8_t* b = rows + lane * kFkRow;
-        const uint32_t e12 = lds_be16(b, 12);
-        const bool eth = len >= 14, tagged = e12 == 0x8100u;
-        const uint32_t sh = tagged ? 4u : 0u;  // l2 = 18 behind a tag
-        const bool known = eth && (!tagged || len >= 18);
-        const uint32_t et = !known ? 0u : tagged ? lds_be16(b, 16) : e12;
-        const bool v4 = known && et == 0x0800u && 34u + sh <= len;  // ipv4() present
-        const uint32_t l4 = 14u + sh + (lds_u8(b, 14u + sh) & 15u) * 4u;
-        {  // the ports end at l4 + 4: past byte 47 only with IPv4 options (IHL >= 8; 7 behind a tag)
-            const bool more = v4 && l4 + 4u > 48u && len > 48u;
-            if (__builtin_amdgcn_ballot_w64(more) != 0) {
-                if (more) {
-                    const uint4* src = (const uint4*)(arena + off);
-#pragma unroll
-                    for (uint32_t j = 3; j < 6; ++j) *(uint4*)(b + 16u * j) = ld16<0>(16u * j < len ? src + j : zl);
-                }
-                __builtin_amdgcn_s_waitcnt(0xc07f);
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
+        hdr_rows_store<kFkRow>(rows, lane, c);
         uint32_t key[8];
-        key[kAkMac0] = eth ? *(const uint32_t*)b : 0u;
-        key[kAkMac1] = eth ? *(const uint32_t*)(b + 4) : 0u;
-        key[kAkMac2] = eth ? *(const uint32_t*)(b + 8) : 0u;
-        const bool has_vid = eth && tagged && len >= 18;
-        key[kAkL2] = (has_vid ? lds_be16(b, 14) & 0x0FFFu : 0u) | (et << 16);
-        uint32_t meta = (eth ? kApEth : 0u) | (has_vid ? kApVlan : 0u) | (known ? kApEtype : 0u);
-        uint32_t sip = 0, dip = 0, ports = 0;
-        if (v4) {
-            sip = __builtin_bswap32(lds_le32(b, 26u + sh));  // ntohl: AclRule holds host order
-            dip = __builtin_bswap32(lds_le32(b, 30u + sh));
-            const uint32_t proto = lds_u8(b, 23u + sh);
-            meta |= kApIpv4 | proto;
-            // tcp() needs l4 + 19 <= len (19-byte TcpHeader), udp() l4 + 8 (packet.hpp:473-541)
-            if ((proto == 6 && l4 + 19u <= len) || (proto == 17 && l4 + 8u <= len)) {
-                meta |= kApPorts;
-                ports = lds_be16(b, l4) | (lds_be16(b, l4 + 2u) << 16);
-            }
-        }
-        key[kAkSrcIp] = sip;
-        key[kAkDstIp] = dip;
-        key[kAkPorts] = ports;
-        key[kAkMeta] = meta;
+        acl_key_lds(rows + lane * kFkRow, arena, lp.off, len, key);  // len is 0 without a scan
         // the waterfall: one wave-uniform scan per list present in the wave
         const uint4* rec = (const uint4*)(ea_lds + kAclRowsBytes + kEaSlotsBytes);
         bool pending = scan;
@@ -2616,32 +2525,7 @@ __global__ __launch_bounds__(kBlock) void egress_acl_kernel(const nfcs_desc* __r
                 const bool mine = bind.x == first;
                 for (uint32_t i = first; i < end; i += kAclGroup) {
                     if (__builtin_amdgcn_ballot_w64(mine && match == NFCS_ACL_NO_MATCH) == 0) break;
-                    // as in acl_eval_kernel: dwords 4..7 first, dwords 0..3 only when a rule of the trip tests them
-                    uint32_t d[kAclGroup], l2 = 0;
-#pragma unroll
-                    for (uint32_t j = 0; j < kAclGroup; ++j) {
-                        const uint4* e = rec + (i + j) * 4u;
-                        const uint4 v1 = e[1], m1 = e[3];
-                        d[j] = (key[4] ^ v1.x) & m1.x;
-                        d[j] |= (key[5] ^ v1.y) & m1.y;
-                        d[j] |= (key[6] ^ v1.z) & m1.z;
-                        d[j] |= (key[7] ^ v1.w) & m1.w;
-                        l2 |= m1.w;
-                    }
-                    if (rfl(l2) & kApNeedL2) {
-#pragma unroll
-                        for (uint32_t j = 0; j < kAclGroup; ++j) {
-                            const uint4* e = rec + (i + j) * 4u;
-                            const uint4 v0 = e[0], m0 = e[2];
-                            d[j] |= (key[0] ^ v0.x) & m0.x;
-                            d[j] |= (key[1] ^ v0.y) & m0.y;
-                            d[j] |= (key[2] ^ v0.z) & m0.z;
-                            d[j] |= (key[3] ^ v0.w) & m0.w;
-                        }
-                    }
-                    uint32_t m = NFCS_ACL_NO_MATCH;
-#pragma unroll
-                    for (uint32_t j = kAclGroup; j-- > 0;) m = d[j] == 0 ? i + j : m;  // descending: the first rule wins
+                    const uint32_t m = acl_scan_trip(rec, i, key);
                     match = (mine && match == NFCS_ACL_NO_MATCH) ? m : match;
                 }
                 if (mine) pending = false;
@@ -2698,7 +2582,7 @@ hipError_t launch_egress_acl(const DevInfo& di, const AclSetDev& set, const uint
     if (n == 0) return hipSuccess;
     if (!item_src || !bypass) item_src = nullptr, bypass = nullptr, n_src = 0;
     // 64 packets per wave, one lane each, XCD-aware order; LDS: the header rows, the sum slots, then the rules
-    const uint32_t g = (n + 255u) / 256u;
+    const uint32_t g = lane_blocks(n);
     const unsigned lds = kAclRowsBytes + kEaSlotsBytes + set.rules_padded * (unsigned)sizeof(AclRec);
     hipLaunchKernelGGL(egress_acl_kernel, dim3(g), dim3(kBlock), lds, stream, desc, n, g, arena, arena_bytes, port, set,
                        action, rule, redirect, denied_pkts, (unsigned long long*)denied_bytes, item_src, bypass, n_src);
@@ -2706,8 +2590,8 @@ hipError_t launch_egress_acl(const DevInfo& di, const AclSetDev& set, const uint
 }
 
 // ---- L2 forwarding: FDB lookup, port / VLAN checks, learning -------------------
-// The L2 block of the switch (switch.hpp:305-326) per packet: a wave takes 64 packets, one lane each,
-// with route_lookup_kernel's descriptor load, liveness test and XCD-aware block order. Everything the
+// The L2 block of the switch (switch.hpp:305-326) per packet: a wave takes 64 packets, one lane each
+// (lane_pkt's descriptor load, liveness test and XCD-aware block order, in its own text). Everything the
 // block reads of a frame — both MACs, the EtherType and the TCI — lies in bytes 0..15, so lane l loads
 // that one 16-byte chunk of packet l itself (non-temporal: the frames are streamed) and no LDS is
 // used. The table (nfcs_fdb.h FdbSlot) is probed per lane from global memory with the default cache
@@ -2740,7 +2624,8 @@ __global__ __launch_bounds__(kBlock) void l2_lookup_kernel(const nfcs_desc* __re
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint64_t p0 = ((uint64_t)xcd_block_n(nblocks) * kWavesPerBlock + rfl(wave)) * 64u;
     if (p0 >= n) return;
-    // lane l: descriptor of packet p0 + l (one coalesced load); dead packets read as length 0
+    // lane_pkt's text, kept here: the descriptor and the route verdict load from one block, so that both are
+    // in flight together (through lane_pkt the verdict's load waits for the descriptor's: +0.5-1.5%, §26)
     const uint64_t p = p0 + lane;
     uint2 dl = make_uint2(0u, 0u);
     uint32_t rtv = NFCS_RT_NOT_IPV4;
@@ -2820,7 +2705,7 @@ hipError_t launch_l2_lookup(const DevInfo& di, const FdbDev& fdb, uint32_t ingre
     (void)di;
     if (n == 0) return hipSuccess;
     // 64 packets per wave, one lane each, XCD-aware order; no LDS
-    const uint32_t g = (n + 255u) / 256u;
+    const uint32_t g = lane_blocks(n);
     if (learn)
         hipLaunchKernelGGL(l2_lookup_kernel<true>, dim3(g), dim3(kBlock), 0, stream, desc, n, g, arena, arena_bytes, fdb,
                            ingress, rt_verdict, egress_port, verdict, vlan, learn);
@@ -2831,9 +2716,8 @@ hipError_t launch_l2_lookup(const DevInfo& di, const FdbDev& fdb, uint32_t ingre
 }
 
 // ---- Egress stage: VLAN egress plan, QoS classify, enqueue ---------------------
-// The plan: process_egress and classify_packet_to_queue per packet, l2_lookup_kernel's shape: a wave takes
-// 64 packets, one lane each, with route_lookup_kernel's descriptor load, liveness test and XCD-aware block
-// order. The decision reads frame bytes 12..19, which straddle chunks 0 and 1: the packet's own lane loads
+// The plan: process_egress and classify_packet_to_queue per packet: a wave takes 64 packets, one lane each
+// (lane_pkt). The decision reads frame bytes 12..19, which straddle chunks 0 and 1: the packet's own lane loads
 // them with ONE 8-byte load at byte 12 (4-byte aligned, as every frame starts on a 16-byte boundary;
 // non-temporal: the frames are streamed), or the 4 bytes 12..15 alone when the frame ends inside chunk 0
 // (chunk 1 may then lie outside the arena). Two 16-byte chunk loads, the first form, touched every frame's
@@ -2855,22 +2739,18 @@ __global__ __launch_bounds__(kBlock) void egress_plan_kernel(const nfcs_desc* __
                                                              uint32_t* __restrict__ port_out,
                                                              uint32_t* __restrict__ ops_out,
                                                              uint8_t* __restrict__ queue_out) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t p0 = ((uint64_t)xcd_block_n(nblocks) * kWavesPerBlock + rfl(wave)) * 64u;
-    if (p0 >= n) return;
-    // lane l: descriptor and ports of packet p0 + l (coalesced loads); dead packets read as length 0
-    const uint64_t p = p0 + lane;
-    uint2 dl = make_uint2(0u, 0u);
+    const LanePkt lp = lane_pkt(desc, n, nblocks, arena_bytes);
+    const uint64_t p = lp.p, off = lp.off;
+    if (lp.p0 >= n) return;
+    // lane l: the ports of packet p0 + l (coalesced loads)
     uint32_t port = NFCS_IF_NONE;
     if (p < n) {
-        dl = ((const uint2*)desc)[p];
         uint32_t l3 = l3_port ? l3_port[p] : NFCS_IF_NONE;
         if (fwd_status && !(fwd_status[p] & NFCS_ST_FLAG_FWD)) l3 = NFCS_IF_NONE;  // masked by the ACL, TTL expired
         port = l3 != NFCS_IF_NONE ? l3 : l2_port ? l2_port[p] : NFCS_IF_NONE;
     }
-    const uint64_t off = (uint64_t)dl.x * 16u;
-    const bool live = p < n && port != NFCS_IF_NONE && off + (((uint64_t)dl.y + 15u) & ~15ull) <= arena_bytes;
-    const uint32_t len = live ? dl.y : 0u;
+    const bool live = lp.live && port != NFCS_IF_NONE;
+    const uint32_t len = live ? lp.d.y : 0u;
     const EgressRec r = eg_rec(eg, port, live);
     // bytes 12..15 lie in chunk 0 once the frame has an Ethernet header; chunk 1 lies inside the arena
     // when len > 16 (the descriptor test covers len rounded up to 16)
@@ -2897,15 +2777,15 @@ hipError_t launch_egress_plan(const DevInfo& di, const EgressDev& eg, const uint
                               hipStream_t stream) {
     (void)di;
     if (n == 0) return hipSuccess;
-    const uint32_t g = (n + 255u) / 256u;
+    const uint32_t g = lane_blocks(n);
     hipLaunchKernelGGL(egress_plan_kernel, dim3(g), dim3(kBlock), 0, stream, desc, n, g, arena, arena_bytes, eg, l3_port,
                        fwd_status, l2_port, port, ops, queue);
     return hipGetLastError();
 }
 
 // ---- Ingress dispatch: what process_received_packet does between the stages ----------
-// l2_lookup_kernel's shape: a wave takes 64 packets, one lane each, with route_lookup_kernel's descriptor load
-// and XCD-aware block order; no loop. The decision is nfcs_switch.h sw_classify, the host walk's own function.
+// A wave takes 64 packets, one lane each (lane_pkt); no loop. The decision is nfcs_switch.h sw_classify, the host
+// walk's own function.
 // A frame is read only where the ingress link is up, the frame is permitted, its descriptor lies inside the
 // arena and it has an Ethernet header: bytes 0..15 with one 16-byte load, and bytes 16..19 (the inner EtherType
 // behind a tag, inside the arena once len > 16) with one 4-byte load where len >= 18. Both loads are issued
@@ -2923,14 +2803,12 @@ __global__ __launch_bounds__(kBlock) void ingress_dispatch_kernel(const nfcs_des
     __shared__ unsigned long long s_bytes[kWavesPerBlock];
     __shared__ uint32_t s_cnt[kWavesPerBlock];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t p0 = ((uint64_t)xcd_block_n(nblocks) * kWavesPerBlock + rfl(wave)) * 64u;
-    if (!COUNT && p0 >= n) return;  // a counting wave past n reaches the barrier with zeros
-    const uint64_t p = p0 + lane;
-    const bool in = p < n;
-    uint2 dl = make_uint2(0u, 0u);
+    const LanePkt lp = lane_pkt(desc, n, nblocks, arena_bytes);
+    if (!COUNT && lp.p0 >= n) return;  // a counting wave past n reaches the barrier with zeros
+    const uint64_t p = lp.p, off = lp.off;
+    const bool in = p < n, live = lp.live;
     uint32_t act = NFCS_ACL_PERMIT, red = NFCS_IF_NONE, rt = NFCS_RT_NOT_IPV4, l2v = NFCS_L2_SKIP;
     if (in) {
-        dl = ((const uint2*)desc)[p];
         if (a.action) act = a.action[p];
         if (a.redirect) red = a.redirect[p];
         rt = a.rt_verdict[p];
@@ -2938,9 +2816,7 @@ __global__ __launch_bounds__(kBlock) void ingress_dispatch_kernel(const nfcs_des
     }
     // is_port_link_up(ingress_port_id) (215): uniform over the launch
     const bool rx_up = a.ingress < ports && (port_state[a.ingress] & kSwLinkUp) != 0;
-    const uint32_t len = dl.y;
-    const uint64_t off = (uint64_t)dl.x * 16u;
-    const bool live = sw_desc_live(dl.x, len, arena_bytes);
+    const uint32_t len = lp.d.y;  // counted also where the frame is not read; 0 past n
     const bool rd0 = in && rx_up && sw_reads_head(act, rt, live, len);
     const bool rd1 = in && rx_up && sw_reads_inner(act, rt, live, len);
     const uint4 c = ld16<1>(rd0 ? (const uint4*)(arena + off) : g_zero_line);
@@ -2996,7 +2872,7 @@ __global__ __launch_bounds__(kBlock) void ingress_dispatch_kernel(const nfcs_des
 hipError_t launch_ingress_dispatch(const DevInfo& di, const FdbDev& fdb, const DispatchArgs& a, hipStream_t stream) {
     (void)di;
     if (a.n == 0) return hipSuccess;
-    const uint32_t g = (a.n + 255u) / 256u;
+    const uint32_t g = lane_blocks(a.n);
     if (a.rx_stats)
         hipLaunchKernelGGL(ingress_dispatch_kernel<true>, dim3(g), dim3(kBlock), 0, stream, a.desc, a.n, g, a.arena,
                            a.arena_bytes, fdb.port_state, fdb.ports, a);
@@ -3219,9 +3095,9 @@ hipError_t launch_egress_enqueue(const DevInfo& di, const EgressDev& eg, const u
 // ---- Flood replication: the egress item list and the frame copies ----------------
 // nfcs_fdb.h flood_expand is the sequential definition; these kernels equal it bit for bit. Tiles of
 // kFloodTile consecutive packets, one 1,024-thread workgroup each, one lane per packet, XCD-aware order:
-//   1. flood_count_kernel: per packet (items, copies, flooded, slot bytes) by flood_classify — l2_lookup_kernel's
-//      descriptor load, the liveness test against copy_base, the plan's port rule, and for a flooded packet the
-//      population count of its flood mask (fdb_flood_word over the VLAN's row of the per-VLAN port bitmap, the
+//   1. flood_count_kernel: per packet (items, copies, flooded, slot bytes) by flood_classify — the
+//      descriptor load, the liveness test (sw_desc_live) against copy_base, the plan's port rule, and for a
+//      flooded packet the population count of its flood mask (fdb_flood_word over the VLAN's row of the per-VLAN port bitmap, the
 //      host walk's function) — summed over the tile into scratch[tile].
 //   2. flood_scan_kernel: ONE workgroup of kFloodScanThreads looping over the tile sums, kFloodScanThreads per
 //      trip with a running carry (no second level): scratch[tile] becomes the tile's exclusive prefix,
@@ -3303,8 +3179,7 @@ DEV FloodLane flood_classify(const FdbDev& fdb, const FloodArgs& a, uint64_t p) 
     FloodLane r{make_uint2(0u, 0u), NFCS_IF_NONE, 0u, 0u, false, 0ull};
     if (p >= a.n) return r;
     r.d = ((const uint2*)a.desc)[p];
-    const uint64_t off = (uint64_t)r.d.x * 16u;
-    if (off + flood_round_up(r.d.y, 16u) > a.copy_base) return r;  // not live
+    if (!sw_desc_live(r.d.x, r.d.y, a.copy_base)) return r;
     r.port = flood_unicast_port(a.l3_port ? a.l3_port[p] : 0u, a.l3_port != nullptr, a.fwd_status ? a.fwd_status[p] : 0u,
                                 a.fwd_status != nullptr, a.l2_port ? a.l2_port[p] : 0u, a.l2_port != nullptr);
     if (r.port != NFCS_IF_NONE) {
@@ -3332,6 +3207,20 @@ DEV void flood_store(FloodSum* s, const FloodAcc& v) {
     s->flooded = v.flooded;
     s->pad = 0u;
     s->bytes = v.bytes;
+}
+// Where a packet stands in the list: what the packets before it call for (the tile's prefix plus the scan
+// inside the tile), where its first entry's bytes begin, and whether the list is still open there. Entry k is
+// emitted iff k < cap and base + (slot bytes up to and including k) <= arena_bytes, so the entry before this
+// packet's first (region at.bytes) was emitted iff `open`.
+struct ListAt : FloodAcc {
+    uint64_t region;
+    bool open;
+};
+DEV ListAt list_at(const FloodSum* tile_prefix, const FloodAcc& exc, uint64_t base, uint32_t cap,
+                   uint64_t arena_bytes) {
+    const FloodAcc at = flood_add(flood_load(tile_prefix), exc);
+    const uint64_t region = flood_sat_add(base, at.bytes);
+    return ListAt{at, region, at.items <= cap && region <= arena_bytes};
 }
 
 __global__ __launch_bounds__(kFloodTile) void flood_count_kernel(const FdbDev fdb, const FloodArgs a, uint32_t tiles,
@@ -3369,15 +3258,11 @@ __global__ __launch_bounds__(kFloodTile) void flood_emit_kernel(const FdbDev fdb
     const FloodLane l = flood_classify(fdb, a, p);
     FloodAcc total;
     const FloodAcc exc = flood_block_scan<kFloodWaves>(flood_acc_of(l), wsum, &total);
-    const FloodAcc at = flood_add(flood_load(sums + tile), exc);  // what the packets before this one call for
-    // item k is emitted iff k < cap and copy_base + (slot bytes up to and including k) <= arena_bytes: the item
-    // before this packet's first (k0 - 1, region at.bytes) was emitted iff
-    const uint64_t region = flood_sat_add(a.copy_base, at.bytes);
-    const bool open = at.items <= a.cap && region <= a.arena_bytes;
+    const ListAt at = list_at(sums + tile, exc, a.copy_base, a.cap, a.arena_bytes);
     uint32_t e = 0;  // how many of this packet's items are emitted
-    if (open && l.cnt) {
+    if (at.open && l.cnt) {
         e = min(l.cnt, a.cap - at.items);
-        if (l.slot) e = (uint32_t)min((uint64_t)e, (a.arena_bytes - region) / l.slot);
+        if (l.slot) e = (uint32_t)min((uint64_t)e, (a.arena_bytes - at.region) / l.slot);
     }
     if (p < a.n) {
         if (!l.flood && e) {  // e = 1: at.items < cap
@@ -3395,7 +3280,7 @@ __global__ __launch_bounds__(kFloodTile) void flood_emit_kernel(const FdbDev fdb
             f_src[exc.flooded] = (uint32_t)p;
         }
         // the totals: from the packet that holds the cut, or from the last packet when nothing is cut
-        if (open && (e < l.cnt || p + 1u == a.n)) {
+        if (at.open && (e < l.cnt || p + 1u == a.n)) {
             const FloodAcc all = flood_load(sums + tiles);
             nfcs_flood_totals t;
             t.items = at.items + e;
@@ -3452,28 +3337,50 @@ __global__ __launch_bounds__(kFloodTile) void flood_emit_kernel(const FdbDev fdb
     }
 }
 
-__global__ __launch_bounds__(kBlock) void flood_pad_kernel(const FloodArgs a) {
+// Entries [*emitted, cap) of a list inert. The flood's and the ICMP responder's emitted counts are the first
+// word of their totals.
+static_assert(offsetof(nfcs_flood_totals, items) == 0, "flood_pad_kernel reads items at the struct's address");
+static_assert(offsetof(nfcs_icmp_totals, messages) == 0, "flood_pad_kernel reads messages at the struct's address");
+// One struct argument, which the waves that get that far read from the kernarg segment (five separate arguments
+// would be preloaded into SGPRs for every wave, and most waves of this kernel leave at the first comparison).
+struct ListOut {
+    nfcs_desc* desc;
+    uint32_t* port;
+    uint32_t* src;
+    uint32_t cap;
+    const uint32_t* emitted;
+};
+__global__ __launch_bounds__(kBlock) void flood_pad_kernel(const ListOut o) {
     const uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (k >= a.cap || k < a.totals->items) return;
-    ((uint2*)a.item_desc)[k] = make_uint2(0u, 0u);
-    a.item_port[k] = NFCS_IF_NONE;
-    a.item_src[k] = NFCS_ITEM_NONE;
+    if (k >= o.cap || k < *o.emitted) return;
+    ((uint2*)o.desc)[k] = make_uint2(0u, 0u);
+    o.port[k] = NFCS_IF_NONE;
+    o.src[k] = NFCS_ITEM_NONE;
+}
+
+// A list stage over n packets: count / flood_scan_kernel / emit / pad. t...: the tables and the stage's
+// arguments, as both of its kernels take them in front of (tiles, sums).
+template <typename... T>
+hipError_t launch_list_stage(void (*count)(T..., uint32_t, FloodSum*), void (*emit)(T..., uint32_t, const FloodSum*),
+                             uint32_t n, const ListOut& out, uint32_t* scratch, hipStream_t stream, const T&... t) {
+    if (n == 0) return hipSuccess;
+    const uint32_t tiles = (uint32_t)(((uint64_t)n + kFloodTile - 1u) / kFloodTile);
+    FloodSum* sums = (FloodSum*)scratch;  // tiles + 1 records (flood_scratch_words)
+    hipLaunchKernelGGL(count, dim3(tiles), dim3(kFloodTile), 0, stream, t..., tiles, sums);
+    hipLaunchKernelGGL(flood_scan_kernel, dim3(1), dim3(kFloodScanThreads), 0, stream, sums, tiles);
+    hipLaunchKernelGGL(emit, dim3(tiles), dim3(kFloodTile), 0, stream, t..., tiles, sums);
+    if (out.cap) {
+        const uint32_t g = (uint32_t)(((uint64_t)out.cap + kBlock - 1u) / kBlock);
+        hipLaunchKernelGGL(flood_pad_kernel, dim3(g), dim3(kBlock), 0, stream, out);
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_flood_expand(const DevInfo& di, const FdbDev& fdb, const FloodArgs& a, uint32_t* scratch,
                                hipStream_t stream) {
     (void)di;
-    if (a.n == 0) return hipSuccess;
-    const uint32_t tiles = (uint32_t)(((uint64_t)a.n + kFloodTile - 1u) / kFloodTile);
-    FloodSum* sums = (FloodSum*)scratch;  // tiles + 1 records (flood_scratch_words)
-    hipLaunchKernelGGL(flood_count_kernel, dim3(tiles), dim3(kFloodTile), 0, stream, fdb, a, tiles, sums);
-    hipLaunchKernelGGL(flood_scan_kernel, dim3(1), dim3(kFloodScanThreads), 0, stream, sums, tiles);
-    hipLaunchKernelGGL(flood_emit_kernel, dim3(tiles), dim3(kFloodTile), 0, stream, fdb, a, tiles, sums);
-    if (a.cap) {
-        const uint32_t g = (uint32_t)(((uint64_t)a.cap + kBlock - 1u) / kBlock);
-        hipLaunchKernelGGL(flood_pad_kernel, dim3(g), dim3(kBlock), 0, stream, a);
-    }
-    return hipGetLastError();
+    const ListOut out = {a.item_desc, a.item_port, a.item_src, a.cap, (const uint32_t*)a.totals};
+    return launch_list_stage(flood_count_kernel, flood_emit_kernel, a.n, out, scratch, stream, fdb, a);
 }
 
 // ---- ICMP responder: echo replies and TTL / unreachable errors -------------------
@@ -3494,7 +3401,7 @@ hipError_t launch_flood_expand(const DevInfo& di, const FdbDev& fdb, const Flood
 //      registers, and stored. The first pass's chunks stay in registers until the row's sum is complete:
 //      chunk 2 then takes the ICMP checksum and the pass is stored. Every message byte is written once and no
 //      byte of the region is read.
-//   4. icmp_pad_kernel: entries [messages, cap) inert.
+//   4. flood_pad_kernel, as it is: entries [messages, cap) inert.
 // No position comes from an atomic and no loop ends on data alone (a message has at most 4,097 chunks).
 constexpr uint32_t kIcmpR = 16, kIcmpK = 6;  // a row pass: 16 lanes x 6 chunks = 1,536 message bytes
 constexpr uint32_t kIcmpRows = kIcmpTile / kIcmpR;
@@ -3505,9 +3412,9 @@ DEV IcmpPlan icmp_classify(const IcmpView& t, const FibView& fib, const IcmpArgs
     *d = make_uint2(0u, 0u);
     if (p < a.n) {
         *d = ((const uint2*)a.desc)[p];
-        const uint64_t off = (uint64_t)d->x * 16u;
-        if (off + flood_round_up(d->y, 16u) <= a.msg_base)  // live
-            return icmp_plan(t, fib, a.ingress, a.arena + off, d->y, a.rt_verdict[p], a.ip_id ? a.ip_id[p] : 0u);
+        if (sw_desc_live(d->x, d->y, a.msg_base))
+            return icmp_plan(t, fib, a.ingress, a.arena + (uint64_t)d->x * 16u, d->y, a.rt_verdict[p],
+                             a.ip_id ? a.ip_id[p] : 0u);
     }
     IcmpPlan r;
     r.status = NFCS_ICMP_ST_NONE;
@@ -3591,12 +3498,9 @@ __global__ __launch_bounds__(kIcmpTile) void icmp_emit_kernel(const IcmpView t, 
     const FloodAcc own = icmp_acc_of(pl, a.msg_align);
     FloodAcc total;
     const FloodAcc exc = flood_block_scan<kFloodWaves>(own, wsum_lds, &total);
-    const FloodAcc at = flood_add(flood_load(sums + tile), exc);  // what the packets before this one call for
-    // message k is emitted iff k < cap and msg_base + (slot bytes up to and including k) <= arena_bytes: the
-    // message before this packet's (region at.bytes) was emitted iff
-    const uint64_t region = flood_sat_add(a.msg_base, at.bytes);
-    const bool open = at.items <= a.cap && region <= a.arena_bytes;
-    const uint32_t e = (open && own.items && at.items < a.cap && a.arena_bytes - region >= own.bytes) ? 1u : 0u;
+    const ListAt at = list_at(sums + tile, exc, a.msg_base, a.cap, a.arena_bytes);
+    const uint64_t region = at.region;
+    const uint32_t e = (at.open && own.items && at.items < a.cap && a.arena_bytes - region >= own.bytes) ? 1u : 0u;
     if (p < a.n) {
         if (a.status) a.status[p] = (uint8_t)((own.items && !e) ? (uint32_t)NFCS_ICMP_ST_OVERFLOW : pl.status);
         if (own.items) {  // exc.items < kIcmpTile: its place among the tile's messages
@@ -3618,7 +3522,7 @@ __global__ __launch_bounds__(kIcmpTile) void icmp_emit_kernel(const IcmpView t, 
             vst16<NFCS_FLOOD_STORE>(out + 1, make_uint4(pl.hdr[4], pl.hdr[5], pl.hdr[6], pl.hdr[7]));
         }
         // the totals: from the packet that holds the cut, or from the last packet when nothing is cut
-        if (open && (e < own.items || p + 1u == a.n)) {
+        if (at.open && (e < own.items || p + 1u == a.n)) {
             const FloodAcc all = flood_load(sums + tiles);
             nfcs_icmp_totals r;
             r.messages = at.items + e;
@@ -3677,28 +3581,11 @@ __global__ __launch_bounds__(kIcmpTile) void icmp_emit_kernel(const IcmpView t, 
     }
 }
 
-__global__ __launch_bounds__(kBlock) void icmp_pad_kernel(const IcmpArgs a) {
-    const uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (k >= a.cap || k < a.totals->messages) return;
-    ((uint2*)a.msg_desc)[k] = make_uint2(0u, 0u);
-    a.msg_port[k] = NFCS_IF_NONE;
-    a.msg_src[k] = NFCS_ITEM_NONE;
-}
-
 hipError_t launch_icmp_respond(const DevInfo& di, const IcmpView& icmp, const FibView& fib, const IcmpArgs& a,
                                uint32_t* scratch, hipStream_t stream) {
     (void)di;
-    if (a.n == 0) return hipSuccess;
-    const uint32_t tiles = (uint32_t)(((uint64_t)a.n + kIcmpTile - 1u) / kIcmpTile);
-    FloodSum* sums = (FloodSum*)scratch;  // tiles + 1 records (flood_scratch_words)
-    hipLaunchKernelGGL(icmp_count_kernel, dim3(tiles), dim3(kIcmpTile), 0, stream, icmp, fib, a, tiles, sums);
-    hipLaunchKernelGGL(flood_scan_kernel, dim3(1), dim3(kFloodScanThreads), 0, stream, sums, tiles);
-    hipLaunchKernelGGL(icmp_emit_kernel, dim3(tiles), dim3(kIcmpTile), 0, stream, icmp, fib, a, tiles, sums);
-    if (a.cap) {
-        const uint32_t g = (uint32_t)(((uint64_t)a.cap + kBlock - 1u) / kBlock);
-        hipLaunchKernelGGL(icmp_pad_kernel, dim3(g), dim3(kBlock), 0, stream, a);
-    }
-    return hipGetLastError();
+    const ListOut out = {a.msg_desc, a.msg_port, a.msg_src, a.cap, (const uint32_t*)a.totals};
+    return launch_list_stage(icmp_count_kernel, icmp_emit_kernel, a.n, out, scratch, stream, icmp, fib, a);
 }
 
 // ---- synthetic config generator (same spec as oracle/nfcs_oracle.c) -----------
@@ -3808,7 +3695,7 @@ __global__ __launch_bounds__(kBlock) void frames_read_kernel(const nfcs_desc* __
     if (pw >= n) return;
     const nfcs_desc d = pick_desc<PW>(load_descw<PW>(desc, pw, n), row);
     const uint64_t off = (uint64_t)d.off16 * 16u;
-    const bool live = pw + row < n && off + (((uint64_t)d.len + 15u) & ~15ull) <= arena_bytes;
+    const bool live = pw + row < n && sw_desc_live(d.off16, d.len, arena_bytes);
     const uint32_t nch = live ? (d.len + 15u) >> 4 : 0u;
     const uint4* src = (const uint4*)(arena + (live ? off : 0));
     uint4 v[K];
