@@ -176,6 +176,13 @@ struct nfcs_ctx {
     hipStream_t eq_stream = nullptr;
     bool eq_used = false;
     bool eq_own = false;
+    // the stage counters' stripes (nfcs_internal.h kCtSlots; all zero between launches), allocated by the first
+    // call that counts; ct_ev orders a call on another stream behind the last user's fold, as eq_ev does for eq_ws
+    uint64_t* ct_ws = nullptr;
+    hipEvent_t ct_ev = nullptr;
+    hipStream_t ct_stream = nullptr;
+    bool ct_used = false;
+    bool ct_own = false;
     uint32_t slot_bytes = 0;  // launch-shape hint (nfcs_ctx_set_slot_bytes); 0 = arena_bytes / n
     // the footprint observations (launch_shape): kObsSlots host-mapped 64-bit slots the kernels
     // write ({generation, mean}), one per recently seen burst (descriptor array, n, arena bytes),
@@ -293,6 +300,40 @@ hipError_t release_eq(nfcs_ctx* c, hipStream_t st) {
     c->eq_used = true;
     c->eq_own = st == c->stream;
     return c->eq_own ? hipSuccess : hipEventRecord(c->eq_ev, st);
+}
+
+// The same for the stage counters' stripes (ct_ws), of one size: allocated and zeroed by the first call that
+// counts, on the host, before that call launches anything. A failed allocation leaves the context as it was.
+hipError_t acquire_ct(nfcs_ctx* c, hipStream_t st) {
+    if (!c->ct_ws) {
+        uint64_t* p = nullptr;
+        const size_t bytes = (size_t)nfcs::kCtSlots * sizeof(uint64_t);
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return hipErrorOutOfMemory;
+        }
+        e = hipMemset(p, 0, bytes);
+        if (e == hipSuccess) e = hipDeviceSynchronize();  // the zeros are there whatever stream counts first
+        if (e != hipSuccess) {
+            (void)hipFree(p);
+            return e;
+        }
+        c->ct_ws = p;
+    } else if (c->ct_used && c->ct_stream != st) {
+        if (c->ct_own) {
+            hipError_t e = hipEventRecord(c->ct_ev, c->stream);
+            if (e != hipSuccess) return e;
+        }
+        return hipStreamWaitEvent(st, c->ct_ev, 0);
+    }
+    return hipSuccess;
+}
+hipError_t release_ct(nfcs_ctx* c, hipStream_t st) {
+    c->ct_stream = st;
+    c->ct_used = true;
+    c->ct_own = st == c->stream;
+    return c->ct_own ? hipSuccess : hipEventRecord(c->ct_ev, st);
 }
 
 int hip_fail(hipError_t e) {
@@ -1065,6 +1106,21 @@ int with_eq_scratch(nfcs_ctx* c, uint64_t words, hipStream_t st, Launch&& launch
     return NFCS_OK;
 }
 
+// launch(ct) on st with the counter scratch (ct_ws) where the call counts, with null where it does not.
+template <class Launch>
+int with_ct_scratch(nfcs_ctx* c, bool counts, hipStream_t st, Launch&& launch) {
+    if (!counts) {
+        NFCS_HIP(launch((uint64_t*)nullptr));
+        return NFCS_OK;
+    }
+    const hipError_t e = acquire_ct(c, st);
+    if (e == hipErrorOutOfMemory) return NFCS_ENOMEM;
+    NFCS_HIP(e);
+    NFCS_HIP(launch(c->ct_ws));
+    NFCS_HIP(release_ct(c, st));
+    return NFCS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1106,6 +1162,7 @@ NFCS_API int nfcs_ctx_create(int device, nfcs_ctx** out) {
     if (e == hipSuccess) e = hipMalloc(&c->d_digest, sizeof(uint64_t));
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ws_ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->eq_ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ct_ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreate(&c->ev0);
     if (e == hipSuccess) e = hipEventCreate(&c->ev1);
     if (e == hipSuccess) e = hipHostMalloc((void**)&c->obs_host, nfcs_ctx::kObsSlots * sizeof(uint64_t), hipHostMallocMapped);
@@ -1135,10 +1192,13 @@ NFCS_API int nfcs_ctx_destroy(nfcs_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->ws_used && !c->ws_own && c->ws_ev) (void)hipEventSynchronize(c->ws_ev);  // a caller stream's last write pass
     if (c->eq_used && !c->eq_own && c->eq_ev) (void)hipEventSynchronize(c->eq_ev);  // a caller stream's last enqueue
+    if (c->ct_used && !c->ct_own && c->ct_ev) (void)hipEventSynchronize(c->ct_ev);  // a caller stream's last fold
     free_host_pipeline(c);
     if (c->d_digest) (void)hipFree(c->d_digest);
     if (c->eq_ws) (void)hipFree(c->eq_ws);
     if (c->eq_ev) (void)hipEventDestroy(c->eq_ev);
+    if (c->ct_ws) (void)hipFree(c->ct_ws);
+    if (c->ct_ev) (void)hipEventDestroy(c->ct_ev);
     if (c->ws) (void)hipFree(c->ws);
     if (c->ws_ev) (void)hipEventDestroy(c->ws_ev);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1811,9 +1871,11 @@ NFCS_API int nfcs_egress_acl_device(nfcs_ctx* c, const nfcs_aclset* s, const uin
     if (((uintptr_t)d_port & 3u) || ((uintptr_t)d_rule & 3u) || ((uintptr_t)d_redirect & 3u) ||
         ((uintptr_t)d_denied_pkts & 3u) || ((uintptr_t)d_denied_bytes & 7u))
         return NFCS_EINVAL;
-    NFCS_HIP(nfcs::launch_egress_acl(c->di, s->dev, d_arena, arena_bytes, d_desc, n, d_port, d_action, d_rule, d_redirect,
-                                     d_denied_pkts, d_denied_bytes, pick(c, stream)));
-    return NFCS_OK;
+    hipStream_t st = pick(c, stream);
+    return with_ct_scratch(c, d_denied_pkts != nullptr, st, [&](uint64_t* ct) {
+        return nfcs::launch_egress_acl(c->di, s->dev, d_arena, arena_bytes, d_desc, n, d_port, d_action, d_rule, d_redirect,
+                                       d_denied_pkts, d_denied_bytes, ct, st);
+    });
 }
 
 // ---- TX queues (nfcs_txq.h: tables, host state, the walks and the closed form) and their kernels ------
@@ -2091,8 +2153,9 @@ NFCS_API int nfcs_ingress_dispatch_device(nfcs_ctx* c, const nfcs_fdb* f, uint32
         return NFCS_EINVAL;
     const nfcs::DispatchArgs a{d_arena, arena_bytes, ingress_port, num_ports, n, d_desc, d_action, d_redirect,
                                d_rt_verdict, d_nh, d_l2_port, d_l2_verdict, d_class, d_bypass, d_rx_stats};
-    NFCS_HIP(nfcs::launch_ingress_dispatch(c->di, f->dev, a, pick(c, stream)));
-    return NFCS_OK;
+    hipStream_t st = pick(c, stream);
+    return with_ct_scratch(c, d_rx_stats != nullptr, st,
+                           [&](uint64_t* ct) { return nfcs::launch_ingress_dispatch(c->di, f->dev, a, ct, st); });
 }
 
 NFCS_API int nfcs_egress_acl_items_host(const nfcs_aclset* s, const uint8_t* arena, uint64_t arena_bytes,
@@ -2121,9 +2184,11 @@ NFCS_API int nfcs_egress_acl_items_device(nfcs_ctx* c, const nfcs_aclset* s, con
     if (((uintptr_t)d_port & 3u) || ((uintptr_t)d_rule & 3u) || ((uintptr_t)d_redirect & 3u) ||
         ((uintptr_t)d_denied_pkts & 3u) || ((uintptr_t)d_denied_bytes & 7u) || ((uintptr_t)d_item_src & 3u))
         return NFCS_EINVAL;
-    NFCS_HIP(nfcs::launch_egress_acl(c->di, s->dev, d_arena, arena_bytes, d_desc, n, d_port, d_action, d_rule, d_redirect,
-                                     d_denied_pkts, d_denied_bytes, pick(c, stream), d_item_src, d_bypass, n_src));
-    return NFCS_OK;
+    hipStream_t st = pick(c, stream);
+    return with_ct_scratch(c, d_denied_pkts != nullptr, st, [&](uint64_t* ct) {
+        return nfcs::launch_egress_acl(c->di, s->dev, d_arena, arena_bytes, d_desc, n, d_port, d_action, d_rule, d_redirect,
+                                       d_denied_pkts, d_denied_bytes, ct, st, d_item_src, d_bypass, n_src);
+    });
 }
 
 }  // extern "C"
@@ -2189,6 +2254,13 @@ NFCS_API int nfcs_switch_rx_device(nfcs_ctx* c, const nfcs_switch_tables* tb, co
     uint8_t *d_queue = ws + w.queue, *d_eact = ws + w.eact;
     const bool acl = tb->ingress_acl != nullptr;
     const uint64_t frames = io->copy_base;  // the frames lie in [0, copy_base); the copies behind are the egress side's
+    // the counter scratch of the dispatch and the egress ACL, before the first launch: without it nothing runs
+    const bool counts = io->d_rx_stats || (cap > 0 && tb->aclset && io->d_denied_pkts);
+    if (counts) {
+        const hipError_t e = acquire_ct(c, st);
+        if (e == hipErrorOutOfMemory) return NFCS_ENOMEM;
+        NFCS_HIP(e);
+    }
     // 1-3: the three decisions (switch.hpp:219-245, 259-301, 305-326)
     NFCS_HIP(nfcs::launch_route_lookup(c->di, tb->fib->dev, io->d_arena, frames, io->d_desc, n, d_nh, d_eif, d_rt, st));
     if (acl)
@@ -2200,7 +2272,8 @@ NFCS_API int nfcs_switch_rx_device(nfcs_ctx* c, const nfcs_switch_tables* tb, co
     const nfcs::DispatchArgs da{io->d_arena, frames, io->ingress_port, io->num_ports, n, io->d_desc,
                                 acl ? d_act : nullptr, acl ? d_red : nullptr, d_rt, d_nh, d_l2p, d_l2v, io->d_class, d_byp,
                                 io->d_rx_stats};
-    NFCS_HIP(nfcs::launch_ingress_dispatch(c->di, tb->fdb->dev, da, st));
+    NFCS_HIP(nfcs::launch_ingress_dispatch(c->di, tb->fdb->dev, da, c->ct_ws, st));
+    if (io->d_rx_stats) NFCS_HIP(release_ct(c, st));
     // 5: the fused forward
     int rc = l3_forward_device(c, io->d_arena, frames, io->d_desc, d_nh, n, tb->fib->d_table, tb->fib->d_table_n, d_st, st);
     if (rc != NFCS_OK) return rc;
@@ -2220,10 +2293,12 @@ NFCS_API int nfcs_switch_rx_device(nfcs_ctx* c, const nfcs_switch_tables* tb, co
         NFCS_HIP(nfcs::launch_vlan(c->di, io->d_arena, io->arena_bytes, io->d_item_desc, cap, d_ops, 0u, nullptr, 0u, nullptr,
                                    st, sh.mean, sh.obs, sh.bits));
     }
-    if (tb->aclset)
+    if (tb->aclset) {
         NFCS_HIP(nfcs::launch_egress_acl(c->di, tb->aclset->dev, io->d_arena, io->arena_bytes, io->d_item_desc, cap,
                                          io->d_item_port, d_eact, nullptr, nullptr, io->d_denied_pkts, io->d_denied_bytes,
-                                         st, io->d_item_src, d_byp, n));
+                                         c->ct_ws, st, io->d_item_src, d_byp, n));
+        if (io->d_denied_pkts) NFCS_HIP(release_ct(c, st));
+    }
     // 10-11: enqueue_packet (qos_manager.cpp:111-153)
     rc = with_eq_scratch(c, nfcs::egress_scratch_words(cap, tb->egress->dev.keys), st, [&](uint32_t* sc) {
         return nfcs::launch_egress_enqueue(c->di, tb->egress->dev, io->d_item_port, d_queue, cap, io->d_depth, nullptr,
@@ -2669,7 +2744,11 @@ NFCS_API int nfcs_digest_device(nfcs_ctx* c, const uint8_t* d_arena, uint64_t ar
     NFCS_HIP(hipMemsetAsync(c->d_digest, 0, sizeof(uint64_t), st));
     if (n) {
         if (!d_arena || !d_desc) return NFCS_EINVAL;
-        NFCS_HIP(nfcs::launch_digest(c->di, d_arena, arena_bytes, d_desc, n, first, c->d_digest, st));
+        const hipError_t e = acquire_ct(c, st);
+        if (e == hipErrorOutOfMemory) return NFCS_ENOMEM;
+        NFCS_HIP(e);
+        NFCS_HIP(nfcs::launch_digest(c->di, d_arena, arena_bytes, d_desc, n, first, c->d_digest, c->ct_ws, st));
+        NFCS_HIP(release_ct(c, st));
     }
     NFCS_HIP(hipMemcpyAsync(h_digest, c->d_digest, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     NFCS_HIP(hipStreamSynchronize(st));

@@ -196,6 +196,20 @@ inline uint32_t demand_sampled_one(uint32_t n) {
     return n / span * kDemandBlockPackets + (rest < kDemandBlockPackets ? rest : kDemandBlockPackets);
 }
 
+// Stage counters: a counting kernel's workgroup adds its sums into one stripe of the
+// context's counter scratch, chosen by its place in the launch, and a fold kernel behind it on the same
+// stream sums the stripes, adds each non-zero sum to the caller's counter with one atomic and leaves the
+// stripes zero. A stripe holds the launch's 64-bit slots on lines of its own: adds on one address are
+// served one after another, so 4,096 workgroups put 64 adds on an address instead of 4,096. The scratch
+// (kCtSlots 64-bit slots, 272 KiB) has one region per user: the dispatch's three counters, the digest's one
+// word, and the egress ACL's {packets, bytes} per port, its stripes round_up(2 * ports, kCtLineSlots) apart.
+constexpr uint32_t kCtStripes = 64;     // the dispatch's and the digest's; a power of two
+constexpr uint32_t kCtAclStripes = 16;  // 16 stripes x 2 x NFCS_L2_MAX_PORTS slots: 256 KiB
+constexpr uint32_t kCtLineSlots = 16;   // 64-bit slots per 128-byte line
+constexpr uint32_t kCtDispatchAt = 0, kCtDigestAt = kCtStripes * kCtLineSlots, kCtAclAt = 2u * kCtStripes * kCtLineSlots;
+constexpr uint32_t kCtSlots = kCtAclAt + kCtAclStripes * 2u * NFCS_L2_MAX_PORTS;
+inline uint32_t ct_acl_stride(uint32_t ports) { return (2u * ports + kCtLineSlots - 1u) & ~(kCtLineSlots - 1u); }
+
 // form kUpdateAuto, sparse: a long-shape call of any size runs as one inline launch (no sub-batches, no
 // records, no write pass), as bursts of at most kInlineMaxPackets do; other shapes are unaffected.
 hipError_t launch_update(const DevInfo& di, uint8_t* arena, uint64_t arena_bytes,
@@ -257,10 +271,12 @@ struct AclSetDev {
 };
 
 // item_src / bypass (both or neither; bypass holds n_src bytes): the items whose source frame is marked bypass
-// the ACL (nfcs_egress_acl_items_device).
+// the ACL (nfcs_egress_acl_items_device). ct: the context's counter scratch (kCtSlots slots, all zero between
+// launches), needed with denied_pkts.
 hipError_t launch_egress_acl(const DevInfo& di, const AclSetDev& set, const uint8_t* arena, uint64_t arena_bytes,
                              const nfcs_desc* desc, uint32_t n, uint32_t* port, uint8_t* action, uint32_t* rule,
-                             uint32_t* redirect, uint32_t* denied_pkts, uint64_t* denied_bytes, hipStream_t stream,
+                             uint32_t* redirect, uint32_t* denied_pkts, uint64_t* denied_bytes, uint64_t* ct,
+                             hipStream_t stream,
                              const uint32_t* item_src = nullptr, const uint8_t* bypass = nullptr, uint32_t n_src = 0);
 
 // The committed L2 tables in device memory (nfcs_fdb_upload; the arrays of FdbTables, nfcs_fdb.h).
@@ -302,7 +318,9 @@ struct DispatchArgs {
     uint8_t* bypass;
     nfcs_rx_stats* rx_stats;
 };
-hipError_t launch_ingress_dispatch(const DevInfo& di, const FdbDev& fdb, const DispatchArgs& a, hipStream_t stream);
+// ct: the context's counter scratch, needed with a.rx_stats.
+hipError_t launch_ingress_dispatch(const DevInfo& di, const FdbDev& fdb, const DispatchArgs& a, uint64_t* ct,
+                                   hipStream_t stream);
 
 hipError_t launch_egress_plan(const DevInfo& di, const EgressDev& eg, const uint8_t* arena, uint64_t arena_bytes,
                               const nfcs_desc* desc, uint32_t n, const uint32_t* l3_port, const uint8_t* fwd_status,
@@ -407,7 +425,7 @@ hipError_t launch_gen_config(const DevInfo& di, int config, uint64_t seed, uint6
                              const nfcs_desc* desc, hipStream_t stream);
 
 hipError_t launch_digest(const DevInfo& di, const uint8_t* arena, uint64_t arena_bytes,
-                         const nfcs_desc* desc, uint32_t n, uint64_t first, uint64_t* d_out,
+                         const nfcs_desc* desc, uint32_t n, uint64_t first, uint64_t* d_out, uint64_t* ct,
                          hipStream_t stream);
 
 hipError_t launch_stream_read(const uint8_t* buf, uint64_t bytes, int form, unsigned long long* sink,

@@ -2466,11 +2466,53 @@ hipError_t launch_acl_eval(const DevInfo& di, const AclDev& acl, const uint8_t* 
 // over that list's range for the lanes bound to it, retire them, repeat. Every list is scanned at most once
 // per wave, and a wave whose packets all leave by one port runs exactly the single-list loop.
 // Deny counters: the denied lanes of a wave are grouped by port (the same waterfall), each group's lengths
-// are summed in a 64-bit LDS slot of its first lane, and that lane adds the group's count and sum to the
-// port's counters: one pair of global atomics per distinct denied port per wave.
-constexpr uint32_t kEaSlotsBytes = kWavesPerBlock * 64u * 8u;  // one u64 per lane
+// are summed in a 64-bit LDS slot of its first lane. The four waves' groups then meet in a table of kBlock
+// entries {port, packets, bytes} in LDS (in the header rows, which no wave needs any more behind a barrier;
+// open addressing, at most kBlock distinct ports, so every port finds an entry within kBlock probes), and
+// one thread per occupied entry adds it to the port's two slots of the workgroup's stripe of the counter
+// scratch (nfcs_internal.h): one pair of global atomics per distinct denied port per workgroup, spread over
+// kCtAclStripes addresses per counter; counter_fold_kernel behind the launch moves the sums to the caller's
+// arrays. A workgroup without a denied packet leaves at the first of these barriers.
+constexpr uint32_t kEaSlotsBytes = kWavesPerBlock * 64u * 8u + 16u;  // one u64 per lane, and the workgroup's flag
+constexpr uint32_t kEaTableBytes = kBlock * 16u;                     // u32 port, u32 packets, u64 bytes per entry
+static_assert(kEaTableBytes <= kAclRowsBytes, "the table lies in the header rows");
 static_assert(kAclRowsBytes + kEaSlotsBytes + NFCS_ACL_MAX_RULES * sizeof(AclRec) < 64u * 1024u,
               "header rows + sum slots + rules stay under 64 KiB of dynamic LDS (no opt-in needed)");
+
+// The fold behind a counting kernel (nfcs_internal.h): thread j sums slot j of the S stripes (`stride` slots
+// apart), stores zero where it read something else, and adds a non-zero sum to the caller's counter with one
+// atomic: out64[j], or with out32 (the egress ACL's pairs) out32[j / 2] for an even j and out64[j / 2] for an
+// odd one. The loads and stores are 8-byte agent-scope accesses, as the adds into the stripes are.
+template <uint32_t S>
+__global__ __launch_bounds__(kBlock) void counter_fold_kernel(unsigned long long* __restrict__ stripes, uint32_t stride,
+                                                              uint32_t slots, unsigned long long* __restrict__ out64,
+                                                              uint32_t* __restrict__ out32) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= slots) return;
+    unsigned long long v[S], sum = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < S; ++k)
+        v[k] = __hip_atomic_load(stripes + (uint64_t)k * stride + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (uint32_t k = 0; k < S; ++k) {
+        if (v[k]) __hip_atomic_store(stripes + (uint64_t)k * stride + j, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sum += v[k];
+    }
+    if (!sum) return;
+    if (!out32)
+        atomicAdd(out64 + j, sum);
+    else if (j & 1u)
+        atomicAdd(out64 + (j >> 1), sum);
+    else
+        atomicAdd(out32 + (j >> 1), (uint32_t)sum);  // a stripe's packets fit 32 bits, and the counter wraps as before
+}
+
+template <uint32_t S>
+void launch_counter_fold(uint64_t* stripes, uint32_t stride, uint32_t slots, uint64_t* out64, uint32_t* out32,
+                         hipStream_t stream) {
+    hipLaunchKernelGGL(counter_fold_kernel<S>, dim3((slots + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream,
+                       (unsigned long long*)stripes, stride, slots, (unsigned long long*)out64, out32);
+}
 
 __global__ __launch_bounds__(kBlock) void egress_acl_kernel(const nfcs_desc* __restrict__ desc, uint32_t n,
                                                             uint32_t nblocks, const uint8_t* __restrict__ arena,
@@ -2478,8 +2520,7 @@ __global__ __launch_bounds__(kBlock) void egress_acl_kernel(const nfcs_desc* __r
                                                             const AclSetDev set, uint8_t* __restrict__ action_out,
                                                             uint32_t* __restrict__ rule_out,
                                                             uint32_t* __restrict__ redirect_out,
-                                                            uint32_t* __restrict__ denied_pkts,
-                                                            unsigned long long* __restrict__ denied_bytes,
+                                                            unsigned long long* __restrict__ ct, uint32_t ct_stride,
                                                             const uint32_t* __restrict__ item_src,
                                                             const uint8_t* __restrict__ bypass, uint32_t n_src) {
     extern __shared__ __attribute__((aligned(16))) uint8_t ea_lds[];
@@ -2509,8 +2550,10 @@ __global__ __launch_bounds__(kBlock) void egress_acl_kernel(const nfcs_desc* __r
     // every list's compiled rules, four 16-byte pieces each, once per workgroup (every wave of the
     // workgroup takes part, also one past n or without a scan: it reaches the barrier)
     stage_to_lds((uint4*)(ea_lds + kAclRowsBytes + kEaSlotsBytes), set.rec, set.rules_padded * 4u);
+    uint32_t* wg_denied = (uint32_t*)(ea_lds + kAclRowsBytes + kEaSlotsBytes - 16u);
+    if (ct && threadIdx.x == 0) *wg_denied = 0u;
     __syncthreads();
-    if (p0 >= n) return;
+    if (!ct && p0 >= n) return;  // a counting wave past n has no scan and no denied lane, and reaches the barriers
     uint32_t match = NFCS_ACL_NO_MATCH;  // an index into the one array
     if (any) {
         hdr_rows_store<kFkRow>(rows, lane, c);
@@ -2547,9 +2590,11 @@ __global__ __launch_bounds__(kBlock) void egress_acl_kernel(const nfcs_desc* __r
         if (redirect_out) redirect_out[p] = redirect;
         if (denied || action == NFCS_ACL_BAD_DESC) port_io[p] = NFCS_IF_NONE;  // a predicated store
     }
-    if (denied_pkts && __builtin_amdgcn_ballot_w64(denied) != 0) {  // denied lanes had a list: port < set.ports
-        unsigned long long* slot = (unsigned long long*)(ea_lds + kAclRowsBytes) + wave * 64u;
-        uint32_t lead = lane, cnt = 0;
+    if (!ct) return;
+    unsigned long long* slot = (unsigned long long*)(ea_lds + kAclRowsBytes) + wave * 64u;
+    uint32_t lead = lane, cnt = 0;
+    bool leader = false;
+    if (__builtin_amdgcn_ballot_w64(denied) != 0) {  // denied lanes had a list: port < set.ports
         bool dp = denied;
         while (__builtin_amdgcn_ballot_w64(dp) != 0) {
             if (dp) {
@@ -2562,30 +2607,59 @@ __global__ __launch_bounds__(kBlock) void egress_acl_kernel(const nfcs_desc* __r
                 }
             }
         }
-        const bool leader = denied && lead == lane;
+        leader = denied && lead == lane;
         if (leader) slot[lane] = 0ull;
         __builtin_amdgcn_wave_barrier();  // one wave's LDS operations execute in order
         if (denied) atomicAdd(&slot[lead], (unsigned long long)dl.y);
-        __builtin_amdgcn_wave_barrier();
-        if (leader) {
-            atomicAdd(&denied_pkts[port], cnt);
-            atomicAdd(&denied_bytes[port], slot[lane]);
+        if (lane == 0) *wg_denied = 1u;
+    }
+    __syncthreads();  // every wave is done with its header rows
+    if (*wg_denied == 0u) return;  // uniform over the workgroup
+    uint32_t* t_port = (uint32_t*)ea_lds;
+    uint32_t* t_cnt = t_port + kBlock;
+    unsigned long long* t_bytes = (unsigned long long*)(t_cnt + kBlock);
+    t_port[threadIdx.x] = NFCS_IF_NONE;  // no port: a denied lane's port is below set.ports
+    t_cnt[threadIdx.x] = 0u;
+    t_bytes[threadIdx.x] = 0ull;
+    __syncthreads();
+    if (leader) {
+        uint32_t h = (port * 0x9E3779B1u) >> 24;  // kBlock = 256 entries
+        static_assert(kBlock == 256, "the hash keeps 8 bits");
+        for (uint32_t k = 0; k < kBlock; ++k, h = (h + 1u) & (kBlock - 1u)) {  // an entry is free or the port's within kBlock probes
+            const uint32_t was = atomicCAS(&t_port[h], (uint32_t)NFCS_IF_NONE, port);
+            if (was == NFCS_IF_NONE || was == port) {
+                atomicAdd(&t_cnt[h], cnt);
+                atomicAdd(&t_bytes[h], slot[lane]);
+                break;
+            }
         }
+    }
+    __syncthreads();
+    const uint32_t tp = t_port[threadIdx.x];
+    if (tp != NFCS_IF_NONE) {
+        unsigned long long* to = ct + (uint64_t)(xcd_block_n(nblocks) % kCtAclStripes) * ct_stride + 2u * tp;
+        atomicAdd(to, (unsigned long long)t_cnt[threadIdx.x]);
+        atomicAdd(to + 1, t_bytes[threadIdx.x]);
     }
 }
 
 hipError_t launch_egress_acl(const DevInfo& di, const AclSetDev& set, const uint8_t* arena, uint64_t arena_bytes,
                              const nfcs_desc* desc, uint32_t n, uint32_t* port, uint8_t* action, uint32_t* rule,
-                             uint32_t* redirect, uint32_t* denied_pkts, uint64_t* denied_bytes, hipStream_t stream,
-                             const uint32_t* item_src, const uint8_t* bypass, uint32_t n_src) {
+                             uint32_t* redirect, uint32_t* denied_pkts, uint64_t* denied_bytes, uint64_t* ct,
+                             hipStream_t stream, const uint32_t* item_src, const uint8_t* bypass, uint32_t n_src) {
     (void)di;
     if (n == 0) return hipSuccess;
     if (!item_src || !bypass) item_src = nullptr, bypass = nullptr, n_src = 0;
+    if (denied_pkts && !ct) return hipErrorInvalidValue;
+    // the stripes of the counter scratch: {packets, bytes} per port, all zero before and after
+    uint64_t* stripes = denied_pkts ? ct + kCtAclAt : nullptr;
+    const uint32_t stride = ct_acl_stride(set.ports);
     // 64 packets per wave, one lane each, XCD-aware order; LDS: the header rows, the sum slots, then the rules
     const uint32_t g = lane_blocks(n);
     const unsigned lds = kAclRowsBytes + kEaSlotsBytes + set.rules_padded * (unsigned)sizeof(AclRec);
     hipLaunchKernelGGL(egress_acl_kernel, dim3(g), dim3(kBlock), lds, stream, desc, n, g, arena, arena_bytes, port, set,
-                       action, rule, redirect, denied_pkts, (unsigned long long*)denied_bytes, item_src, bypass, n_src);
+                       action, rule, redirect, (unsigned long long*)stripes, stride, item_src, bypass, n_src);
+    if (stripes && set.ports) launch_counter_fold<kCtAclStripes>(stripes, stride, 2u * set.ports, denied_bytes, denied_pkts, stream);
     return hipGetLastError();
 }
 
@@ -2793,13 +2867,16 @@ hipError_t launch_egress_plan(const DevInfo& di, const EgressDev& eg, const uint
 // frames are streamed. The redirect port's state byte is gathered by the redirecting lanes only.
 // COUNT (d_rx_stats given): packets (one per frame, two per dropped frame) and drops are packed into one
 // word, the bytes are 64-bit; both are summed across the wave by xor shuffles, the four wave sums meet in LDS,
-// and thread 0 adds the workgroup's sums with at most one 64-bit vector atomic per counter.
+// and thread 0 adds the workgroup's sums with at most one 64-bit vector atomic per counter, into the workgroup's
+// stripe of the counter scratch (nfcs_internal.h); counter_fold_kernel behind the launch adds the stripes' sums
+// to rx_stats[ingress]. With the ingress link down no stripe is touched and the fold adds nothing.
 template <bool COUNT>
 __global__ __launch_bounds__(kBlock) void ingress_dispatch_kernel(const nfcs_desc* __restrict__ desc, uint32_t n,
                                                                   uint32_t nblocks, const uint8_t* __restrict__ arena,
                                                                   uint64_t arena_bytes,
                                                                   const uint8_t* __restrict__ port_state, uint32_t ports,
-                                                                  const DispatchArgs a) {
+                                                                  const DispatchArgs a,
+                                                                  unsigned long long* __restrict__ ct) {
     __shared__ unsigned long long s_bytes[kWavesPerBlock];
     __shared__ uint32_t s_cnt[kWavesPerBlock];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -2861,7 +2938,7 @@ __global__ __launch_bounds__(kBlock) void ingress_dispatch_kernel(const nfcs_des
                 tc += s_cnt[w];
                 tb += s_bytes[w];
             }
-            unsigned long long* rx = (unsigned long long*)(a.rx_stats + a.ingress);
+            unsigned long long* rx = ct + (xcd_block_n(nblocks) % kCtStripes) * kCtLineSlots;  // the workgroup's stripe
             if (tc & 0xFFFFu) atomicAdd(rx + 0, (unsigned long long)(tc & 0xFFFFu));
             if (tb) atomicAdd(rx + 1, tb);
             if (tc >> 16) atomicAdd(rx + 2, (unsigned long long)(tc >> 16));
@@ -2869,16 +2946,23 @@ __global__ __launch_bounds__(kBlock) void ingress_dispatch_kernel(const nfcs_des
     }
 }
 
-hipError_t launch_ingress_dispatch(const DevInfo& di, const FdbDev& fdb, const DispatchArgs& a, hipStream_t stream) {
+hipError_t launch_ingress_dispatch(const DevInfo& di, const FdbDev& fdb, const DispatchArgs& a, uint64_t* ct,
+                                   hipStream_t stream) {
     (void)di;
     if (a.n == 0) return hipSuccess;
     const uint32_t g = lane_blocks(a.n);
-    if (a.rx_stats)
+    if (a.rx_stats) {
+        if (!ct) return hipErrorInvalidValue;
+        static_assert(sizeof(nfcs_rx_stats) == 3u * sizeof(uint64_t), "rx_packets, rx_bytes, rx_drops: the three slots");
+        uint64_t* stripes = ct + kCtDispatchAt;
         hipLaunchKernelGGL(ingress_dispatch_kernel<true>, dim3(g), dim3(kBlock), 0, stream, a.desc, a.n, g, a.arena,
-                           a.arena_bytes, fdb.port_state, fdb.ports, a);
-    else
+                           a.arena_bytes, fdb.port_state, fdb.ports, a, (unsigned long long*)stripes);
+        if (a.ingress < fdb.ports)  // else the link reads as down and no stripe was touched
+            launch_counter_fold<kCtStripes>(stripes, kCtLineSlots, 3u, (uint64_t*)(a.rx_stats + a.ingress), nullptr, stream);
+    } else {
         hipLaunchKernelGGL(ingress_dispatch_kernel<false>, dim3(g), dim3(kBlock), 0, stream, a.desc, a.n, g, a.arena,
-                           a.arena_bytes, fdb.port_state, fdb.ports, a);
+                           a.arena_bytes, fdb.port_state, fdb.ports, a, (unsigned long long*)nullptr);
+    }
     return hipGetLastError();
 }
 
@@ -3871,7 +3955,7 @@ __global__ __launch_bounds__(kBlock) void digest_kernel(const uint8_t* __restric
                                                         uint64_t arena_bytes,
                                                         const nfcs_desc* __restrict__ desc,
                                                         uint32_t n, uint64_t first,
-                                                        unsigned long long* __restrict__ out) {
+                                                        unsigned long long* __restrict__ ct) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t nw = gridDim.x * kWavesPerBlock;
     uint64_t wsum = 0;  // uniform
@@ -3898,17 +3982,30 @@ __global__ __launch_bounds__(kBlock) void digest_kernel(const uint8_t* __restric
         const uint64_t h = mix64((uint64_t)len * 0xD6E8FEB86659FD93ull + wave_sum64(acc));
         wsum += mix64(h ^ ((first + p) * 0xA0761D6478BD642Full));
     }
-    if (lane == 0 && wsum) atomicAdd(out, (unsigned long long)wsum);
+    // the four waves' sums meet in LDS (every wave leaves its loop and reaches the barrier), and thread 0 adds the
+    // workgroup's sum to its stripe of the counter scratch (nfcs_internal.h); counter_fold_kernel adds them to *out
+    __shared__ unsigned long long s_sum[kWavesPerBlock];
+    if (lane == 0) s_sum[threadIdx.x >> 6] = wsum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t = 0;
+#pragma unroll
+        for (int w = 0; w < kWavesPerBlock; ++w) t += s_sum[w];
+        if (t) atomicAdd(ct + (blockIdx.x % kCtStripes) * kCtLineSlots, t);
+    }
 }
 
 hipError_t launch_digest(const DevInfo& di, const uint8_t* arena, uint64_t arena_bytes,
-                         const nfcs_desc* desc, uint32_t n, uint64_t first, uint64_t* d_out,
+                         const nfcs_desc* desc, uint32_t n, uint64_t first, uint64_t* d_out, uint64_t* ct,
                          hipStream_t stream) {
     if (n == 0) return hipSuccess;
+    if (!ct) return hipErrorInvalidValue;
     uint32_t grid = (n + kWavesPerBlock - 1) / kWavesPerBlock;
     if (grid > (uint32_t)di.cus * 8u) grid = (uint32_t)di.cus * 8u;
+    uint64_t* stripes = ct + kCtDigestAt;
     hipLaunchKernelGGL(digest_kernel, dim3(grid), dim3(kBlock), 0, stream, arena, arena_bytes,
-                       desc, n, first, (unsigned long long*)d_out);
+                       desc, n, first, (unsigned long long*)stripes);
+    launch_counter_fold<kCtStripes>(stripes, kCtLineSlots, 1u, d_out, nullptr, stream);
     return hipGetLastError();
 }
 
