@@ -179,28 +179,44 @@ def assert_dispatch(got, want, cls, rx=None, ingress=None, what=""):
 
 # ---- the chain on the new host calls ------------------------------------------------------------------------
 
-def host_switch_rx(t, bursts, align=128, copy_align=128, egress_acl=True):
+def per_burst(v, b, default):
+    """A keyword that is one value for every burst or a list with one per burst; None: the default."""
+    v = v[b] if isinstance(v, (list, tuple)) else v
+    return default if v is None else int(v)
+
+
+EXTRA = ("cls", "rx_stats", "totals", "idesc", "isrc", "iport", "iqueue", "order", "key_start", "key_dropped", "tx_raw")
+
+
+def host_switch_rx(t, bursts, align=128, copy_align=128, egress_acl=True, cap=None, region=None, null=(), cut=False):
     """switch_common.host_switch with the library's ingress_dispatch_host and egress_acl_items_host in the place of
-    glue(): the same result structure, plus cls (per burst, the SW_* class of every frame) and rx_stats (per burst,
-    the RX counters of every port after it). egress_acl False: the chain of a switch without egress lists."""
+    glue(): the same result structure, plus cls (per burst, the SW_* class of every frame), rx_stats (per burst,
+    the RX counters of every port after it) and, per burst, what the composite hands out: totals, idesc, isrc, iport
+    (after the egress ACL), iqueue (the plan's queue per item; the host chain only: the composite keeps it in its
+    workspace), order, key_start, key_dropped, and tx_raw = (tx, tx_start, tx_queue) of the dequeue.
+    egress_acl False: the chain of a switch without egress lists. cap / region: the item capacity and the bytes of
+    the copy region, one value or one per burst (default: FANOUT items per frame and room for all of them). Every item
+    must fit unless the caller says cut=True. null: of "ingress_acl", "txq", "rx_stats", "key_dropped", what the device call leaves NULL
+    (nothing is dequeued without txq)."""
     ports, keys = t["eg"].keys()
-    res = dict(sw.empty_result(), cls=[], rx_stats=[])
+    caps, regions = cap, region
+    res = dict(sw.empty_result(), **{k: [] for k in EXTRA})
     depth, dropped = np.zeros(keys, np.uint32), np.zeros(keys, np.uint32)
     acl_ports = max(t["aclset"].info()[0], 1)
     denied_pkts, denied_bytes = np.zeros(acl_ports, np.uint32), np.zeros(acl_ports, np.uint64)
     rx = np.zeros(t["num_ports"], nf.RX_STATS_DTYPE)
     nht = t["fib"].nexthops_host().view(np.uint8).reshape(-1, 12)
-    firsts, idescs, srcs, arenas = [], [], [], []
+    firsts, idescs, srcs, arenas, tx_cap = [], [], [], [], 0
     with sw.make_txq(t) as txq:
         for b, (ingress, first, frames, budget) in enumerate(bursts):
-            cap = sw.FANOUT * len(frames)
-            arena, desc, copy_base = pack_with_tail(frames, align, sw.region_bytes(frames, copy_align))
-            s = stage_inputs(t, ingress, frames)
-            d = dispatch_host(t, ingress, arena, copy_base, desc, s, rx_stats=rx)
+            cap = per_burst(caps, b, sw.FANOUT * len(frames))
+            arena, desc, copy_base = pack_with_tail(frames, align, per_burst(regions, b, sw.region_bytes(frames, copy_align)))
+            s = stage_inputs(t if "ingress_acl" not in null else dict(t, ingress_acl={}), ingress, frames)
+            d = dispatch_host(t, ingress, arena, copy_base, desc, s, rx_stats=None if "rx_stats" in null else rx)
             st = oracle.l3_forward_batch(arena[:copy_base], desc, d["nh"], nht)
             ex = t["fdb"].flood_expand_host(ingress, t["num_ports"], arena.nbytes, copy_base, copy_align, desc, cap, l3_port=s["eif"],
                                             fwd_status=st, l2_port=d["l2_port"], l2_verdict=d["l2_verdict"], l2_vlan=s["l2vlan"])
-            assert int(ex["totals"]["items"]) == int(ex["totals"]["items_needed"])
+            assert cut or int(ex["totals"]["items"]) == int(ex["totals"]["items_needed"])
             arena = copy_model(arena, desc, ex, copy_base)
             idesc = ex["item_desc"].copy()
             ops, queue = plan_host(t["eg"], ex["item_port"], oracle.unpack_frames(arena, idesc))
@@ -210,10 +226,20 @@ def host_switch_rx(t, bursts, align=128, copy_align=128, egress_acl=True):
             if egress_acl:
                 port = t["aclset"].egress_acl_items_host(arena, idesc, port, ex["item_src"], d["bypass"], denied_pkts, denied_bytes)["port"]
             r = t["eg"].enqueue_host(port, queue, depth)
-            txq.append_host(r["order"], r["key_start"], r["depth"], cap, handle=(b << 32) + np.arange(cap, dtype=np.uint64))
-            want = txq.dequeue_host(r["depth"], cap * (b + 1), budget=budget)
+            tx_cap += cap
+            if "txq" in null:
+                want = {"depth": r["depth"], "tx": np.zeros(0, np.uint64), "tx_start": np.zeros(ports + 1, np.uint32),
+                        "tx_queue": np.zeros(0, np.uint8)}
+            else:
+                txq.append_host(r["order"], r["key_start"], r["depth"], cap, handle=(b << 32) + np.arange(cap, dtype=np.uint64))
+                want = txq.dequeue_host(r["depth"], tx_cap, budget=budget)
             depth = want["depth"]
-            dropped = dropped + r["key_dropped"]
+            for k, v in (("totals", ex["totals"]), ("idesc", idesc), ("isrc", ex["item_src"]), ("iport", port), ("iqueue", queue), ("order", r["order"]),
+                         ("key_start", r["key_start"]), ("key_dropped", r["key_dropped"]),
+                         ("tx_raw", (want["tx"], want["tx_start"], want.get("tx_queue")))):
+                res[k].append(v)
+            if "key_dropped" not in null:  # a call that is not handed the array reports no tail drops
+                dropped = dropped + r["key_dropped"]
             firsts.append(first), idescs.append(idesc), srcs.append(ex["item_src"]), arenas.append(arena)
             sw.collect(res, firsts, ports, want, idescs, srcs, arenas, b)
             for k, v in (("depth", depth), ("dropped", dropped), ("denied_pkts", denied_pkts), ("denied_bytes", denied_bytes),
@@ -280,69 +306,129 @@ def device_dispatch(engine, fdb, ingress, num_ports, arena, arena_bytes, desc, s
     return got
 
 
-def snapshot(engine, g, *pairs):
-    """Device-to-device copies of (buffer, bytes) pairs, queued on the engine's stream behind what was launched."""
+def snapshot(engine, g, *pairs, stream=None):
+    """Device-to-device copies of (buffer, bytes) pairs, queued on the engine's stream (or `stream`) behind what was
+    launched there."""
     out = []
     for src, nbytes in pairs:
         dst = g.out(nbytes)
         rc = nf.lib().hipMemcpyAsync(ctypes.c_void_p(dst.ptr), ctypes.c_void_p(src.ptr), ctypes.c_size_t(nbytes), 3,
-                                     ctypes.c_void_p(engine.stream))  # 3: hipMemcpyDeviceToDevice
+                                     ctypes.c_void_p(stream or engine.stream))  # 3: hipMemcpyDeviceToDevice
         assert rc == 0, f"hipMemcpyAsync: {rc}"
         out.append(dst)
     return out
 
 
-def device_switch_rx(engine, t, bursts, align=128, copy_align=128, egress_acl=True):
+def device_switch_rx(engine, t, bursts, align=128, copy_align=128, egress_acl=True, cap=None, region=None, null=(), workspace=None,
+                     ws_bytes=None, stream=None):
     """The bursts through switch_rx_device and txq_dequeue_device: every burst is launched before anything is
     downloaded; depths, deny counters, RX counters and TX rings stay on the device and go on counting. What they
     held after each burst is kept by device-to-device copies queued on the same stream. Returns host_switch_rx's
-    structure."""
+    structure. cap, region: as host_switch_rx's. null: of "ingress_acl", "txq", "rx_stats", "cls", "key_dropped", what
+    the call is handed as NULL (without txq nothing is appended or dequeued). workspace: a (buffer, bytes) pair every
+    burst uses instead of one of its own; ws_bytes: the size the call is told instead of
+    switch_rx_workspace_bytes(n, cap) (the workspace is allocated that large). stream: a caller's stream for the first
+    burst's call, dequeue and state copies; the later bursts run on the context's own with no host synchronisation
+    before them: the context's stream waits on the device for an event recorded behind the first burst (depths,
+    counters and rings are the caller's data, and their order across streams is the caller's to keep)."""
     for obj in [t["fib"], t["fdb"], t["eg"], t["aclset"], *t["ingress_acl"].values()]:
         obj.upload(engine)
     ports, keys = t["eg"].keys()
     acl_ports = max(t["aclset"].info()[0], 1)
     g = Guarded(engine)
+    try:
+        return _switch_rx_bursts(engine, t, bursts, g, ports, keys, acl_ports, align, copy_align, egress_acl, cap, region, null,
+                                 workspace, ws_bytes, stream)
+    finally:
+        g.free()  # also where the call is refused: a test that asks for a refusal leaves no device buffer behind
+
+
+def _switch_rx_bursts(engine, t, bursts, g, ports, keys, acl_ports, align, copy_align, egress_acl, cap, region, null, workspace,
+                      ws_bytes, stream):
     d_depth, d_dpk = g.up(np.zeros(keys, np.uint32), np.uint32), g.up(np.zeros(acl_ports, np.uint32), np.uint32)
     d_dby, d_rx = g.up(np.zeros(acl_ports, np.uint64), np.uint64), g.up(np.zeros(t["num_ports"], nf.RX_STATS_DTYPE), nf.RX_STATS_DTYPE)
-    res = dict(sw.empty_result(), cls=[], rx_stats=[])
-    launched = []
+    res = dict(sw.empty_result(), **{k: [] for k in EXTRA})
+    launched, tx_cap = [], 0
     with sw.make_txq(t, engine) as txq:
         for b, (ingress, first, frames, budget) in enumerate(bursts):
-            n, cap = len(frames), sw.FANOUT * len(frames)
-            tx_cap = cap * (b + 1)
-            arena, desc, copy_base = pack_with_tail(frames, align, sw.region_bytes(frames, copy_align))
+            n, cap_b = len(frames), per_burst(cap, b, sw.FANOUT * len(frames))
+            tx_cap += cap_b
+            arena, desc, copy_base = pack_with_tail(frames, align, per_burst(region, b, sw.region_bytes(frames, copy_align)))
             d_arena, d_desc = g.up(arena, np.uint8), g.up(desc, nf.DESC_DTYPE)
-            d_idesc, d_iport, d_isrc, d_tot = g.out(8 * cap), g.out(4 * cap), g.out(4 * cap), g.out(32)
-            d_order, d_ks, d_kd, d_cls = g.out(4 * cap), g.out(4 * (keys + 1)), g.out(4 * keys), g.out(n)
-            d_tx, d_start = g.out(8 * tx_cap), g.out(4 * (ports + 1))
-            ws_bytes = nf.switch_rx_workspace_bytes(n, cap)
-            d_ws = g.out(ws_bytes)
+            d_idesc, d_iport, d_isrc, d_tot = g.out(8 * cap_b), g.out(4 * cap_b), g.out(4 * cap_b), g.out(32)
+            d_order, d_ks = g.out(4 * cap_b), g.out(4 * (keys + 1))
+            d_kd, d_cls = None if "key_dropped" in null else g.out(4 * keys), None if "cls" in null else g.out(n)
+            d_tx, d_start, d_txq = g.out(8 * tx_cap), g.out(4 * (ports + 1)), g.out(tx_cap)
+            need = nf.switch_rx_workspace_bytes(n, cap_b) if ws_bytes is None else ws_bytes
+            d_ws, told = (g.out(need), need) if workspace is None else workspace
             engine.switch_rx_device(t["fib"], t["fdb"], t["eg"], ingress, t["num_ports"], d_arena, arena.nbytes, copy_base, copy_align,
-                                    d_desc, n, cap, d_depth, d_idesc, d_iport, d_isrc, d_tot, d_order, d_ks, d_ws, ws_bytes,
-                                    ingress_acl=t["ingress_acl"].get(ingress), aclset=t["aclset"] if egress_acl else None, txq=txq,
+                                    d_desc, n, cap_b, d_depth, d_idesc, d_iport, d_isrc, d_tot, d_order, d_ks, d_ws, told,
+                                    ingress_acl=None if "ingress_acl" in null else t["ingress_acl"].get(ingress),
+                                    aclset=t["aclset"] if egress_acl else None, txq=None if "txq" in null else txq,
                                     denied_pkts=d_dpk if egress_acl else None, denied_bytes=d_dby if egress_acl else None,
-                                    rx_stats=d_rx, key_dropped=d_kd, cls=d_cls, handle_base=b << 32)
-            engine.txq_dequeue_device(txq, d_depth, d_tx, tx_cap, d_start, budget=g.up(budget, np.uint32))
-            launched.append((first, arena.nbytes, d_arena, d_idesc, d_isrc, d_tx, tx_cap, d_start, d_kd, d_cls, n, cap,
+                                    rx_stats=None if "rx_stats" in null else d_rx, key_dropped=d_kd, cls=d_cls, handle_base=b << 32,
+                                    stream=stream if b == 0 else None)
+            if "txq" not in null:
+                engine.txq_dequeue_device(txq, d_depth, d_tx, tx_cap, d_start, budget=g.up(budget, np.uint32), tx_queue=d_txq,
+                                          stream=stream if b == 0 else None)
+            launched.append((first, arena.nbytes, d_arena, d_idesc, d_isrc, d_tx, tx_cap, d_start, d_kd, d_cls, n, cap_b, d_iport, d_tot,
+                             d_order, d_ks, d_txq,
                              snapshot(engine, g, (d_depth, 4 * keys), (d_dpk, 4 * acl_ports), (d_dby, 8 * acl_ports),
-                                      (d_rx, 24 * t["num_ports"]))))
+                                      (d_rx, 24 * t["num_ports"]), stream=stream if b == 0 else None)))
+            if stream and b == 0:
+                hip, ev = nf.lib(), ctypes.c_void_p()
+                assert hip.hipEventCreate(ctypes.byref(ev)) == 0 and hip.hipEventRecord(ev, ctypes.c_void_p(stream)) == 0
+                assert hip.hipStreamWaitEvent(ctypes.c_void_p(engine.stream), ev, 0) == 0 and hip.hipEventDestroy(ev) == 0
+        if stream:
+            engine.sync(stream)
         engine.sync()
         dropped = np.zeros(keys, np.uint32)
         firsts, idescs, srcs, arenas = [], [], [], []
-        for b, (first, nbytes, d_arena, d_idesc, d_isrc, d_tx, tx_cap, d_start, d_kd, d_cls, n, cap, snap) in enumerate(launched):
-            firsts.append(first), idescs.append(d_idesc.download(nf.DESC_DTYPE, cap)), srcs.append(d_isrc.download(np.uint32, cap))
+        for b, (first, nbytes, d_arena, d_idesc, d_isrc, d_tx, tx_cap, d_start, d_kd, d_cls, n, cap_b, d_iport, d_tot, d_order, d_ks,
+                d_txq, snap) in enumerate(launched):
+            firsts.append(first), idescs.append(d_idesc.download(nf.DESC_DTYPE, cap_b)), srcs.append(d_isrc.download(np.uint32, cap_b))
             arenas.append(d_arena.download(np.uint8, nbytes))
-            start = d_start.download(np.uint32, ports + 1)
-            tx = d_tx.download(np.uint64, tx_cap)
-            assert (tx[int(start[ports]):] == 0xEEEEEEEEEEEEEEEE).all(), "d_tx was written past tx_start[ports]"
+            if "txq" in null:
+                start, tx, txqueue = np.zeros(ports + 1, np.uint32), np.zeros(0, np.uint64), np.zeros(0, np.uint8)
+            else:
+                start = d_start.download(np.uint32, ports + 1)
+                tx, txqueue = d_tx.download(np.uint64, tx_cap), d_txq.download(np.uint8, tx_cap)
+                assert (tx[int(start[ports]):] == 0xEEEEEEEEEEEEEEEE).all(), "d_tx was written past tx_start[ports]"
+                tx, txqueue = tx[:int(start[ports])], txqueue[:int(start[ports])]
             sw.collect(res, firsts, ports, {"tx": tx, "tx_start": start}, idescs, srcs, arenas, b)
-            dropped = dropped + d_kd.download(np.uint32, keys)
+            kd = np.zeros(keys, np.uint32) if d_kd is None else d_kd.download(np.uint32, keys)
+            dropped = dropped + kd
             res["depth"].append(snap[0].download(np.uint32, keys)), res["dropped"].append(dropped.copy())
             res["denied_pkts"].append(snap[1].download(np.uint32, acl_ports)), res["denied_bytes"].append(snap[2].download(np.uint64, acl_ports))
             res["rx_stats"].append(snap[3].download(nf.RX_STATS_DTYPE, t["num_ports"]))
             res["rx_drops"].append(int(res["rx_stats"][-1][bursts[b][0]]["rx_drops"]))
             res["arena"].append(arenas[-1])
-            res["cls"].append(d_cls.download(np.uint8, n))
+            res["cls"].append(None if d_cls is None else d_cls.download(np.uint8, n))
+            key_start = d_ks.download(np.uint32, keys + 1)
+            order = d_order.download(np.uint32, cap_b)
+            for k, v in (("totals", d_tot.download(nf.FLOOD_TOTALS_DTYPE, 1)[0]), ("idesc", idescs[-1]), ("isrc", srcs[-1]),
+                         ("iport", d_iport.download(np.uint32, cap_b)), ("iqueue", None), ("order", order), ("key_start", key_start),
+                         ("key_dropped", None if d_kd is None else kd), ("tx_raw", (tx, start, txqueue))):
+                res[k].append(v)
         g.check()
-    g.free()
     return res
+
+
+def assert_same_rx(got, want, what=""):
+    """What switch_common.assert_same does not cover: classes, RX counters and every array the composite hands out
+    (order only where items were enqueued: the rest of it is not defined), the raw dequeue record."""
+    for b in range(len(want["cls"])):
+        w = f"{what}burst {b}: "
+        if got["cls"][b] is not None:
+            assert np.array_equal(got["cls"][b], want["cls"][b]), w + "classes"
+        assert np.array_equal(got["rx_stats"][b], want["rx_stats"][b]), w + "RX counters"
+        for k in nf.FLOOD_TOTALS_DTYPE.names:
+            assert int(got["totals"][b][k]) == int(want["totals"][b][k]), w + "totals." + k
+        for k in ("idesc", "isrc", "iport", "key_start"):
+            assert np.array_equal(got[k][b], want[k][b]), w + k
+        if got["key_dropped"][b] is not None:
+            assert np.array_equal(got["key_dropped"][b], want["key_dropped"][b]), w + "key_dropped"
+        m = int(want["key_start"][b][-1])
+        assert np.array_equal(got["order"][b][:m], want["order"][b][:m]), w + "order"
+        for x, y, name in zip(got["tx_raw"][b], want["tx_raw"][b], ("tx", "tx_start", "tx_queue")):
+            assert np.array_equal(x, y), w + name
